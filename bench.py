@@ -15,14 +15,21 @@ FFHQ-1024 StyleGAN2 + clip_loss, batch 4.  N>1 = BASELINE configs[3]: the same s
 per-GPU batch, so that a 1 -> N ratio can be taken at equal per-GPU work.
 Weights are random-init of the real architectures (no network for checkpoints), data is synthetic.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does only what that line's headline needs: set-up,
+the untimed stabilisation loop, --warmup steps, --steps timed steps.  `--full` adds everything else the benchmark measures: the
+bf16x3 / fp16-CLIP previews, `n1_b8`, `config3`, `config5`, `n1_equal_batch` (N > 1), and two extra objects:
   roofline     -- the ModulatedConv2d 3x3 convs of the step (direct MFMA kernels + the two Winograd F(4x4,3x3) forms, all own kernels):
                   FLOPs the matrix pipes EXECUTE / HIP-event time vs the fp32-MFMA peak (`frac` <= 1 by construction); `dominant_kernel`
                   = w2e::modconv_kernel alone; `effective_tflops` = the direct-form (algorithmic) FLOPs of the same calls over the same time
                   (the Winograd forms execute 1/4 of them) -- an effective rate, not a roofline fraction
   cpu_baseline -- the CPU oracle (a port of the reference algorithm) timed on this box's host cores
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (float32), so that two builds can be compared output for
+output: the step's loss terms, the mapper gradients and the mapper parameters after its optimizer step (workloads 2 and 3), or the
+pipeline's outputs (workload 5).  The mapper state the stabilisation loop trained is put back before the warm-up, so the last timed step
+sees the same inputs in every run with the same arguments.
 """
 import argparse
+import functools
 import json
 import os
 import sys
@@ -37,6 +44,8 @@ sys.path.insert(0, ROOT)
 G_FWD_GFLOP_1024 = 148.13  # 3x3 modconv stack per image forward (ToRGB's 0.39 is not MFMA work)
 BF16_MFMA_PEAK_TFLOPS = 2500.0  # dense bf16 MFMA (MI355X_MICROARCH.md); only quoted with --conv-precision bf16x3
 FP32_MFMA_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, dense
+DUMP_MAX_ELEMS = 1 << 22  # --dump-outputs: per array (16 MB of float32); a larger output is written as a fixed, seeded sample of this size
+DUMP_MAX_BYTES = 64 * 10 ** 6  # --dump-outputs: all arrays together (the workload-2 step writes 25 MB, the workload-5 pipeline 34 MB)
 
 
 def make_opts(size, batch, workload=2):
@@ -117,6 +126,63 @@ def make_mask(coach, batch, size, rank, device, synthetic=False):
         return mask
     res = 4 * 2 ** ((13 - 1) // 3) if size == 1024 else max(4, size // 16)  # seeded U(0,1) at the resolution of layer 13
     return torch.rand(batch, 1, res, res, generator=torch.Generator().manual_seed(77 + rank)).to(device)
+
+
+@functools.lru_cache(maxsize=None)
+def dump_sample_indices(n):
+    return torch.randperm(n, generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMS].sort().values
+
+
+def host_arrays(outputs):
+    """--dump-outputs: {name: tensor | number | list of tensors} -> {name: float32 numpy array} on the host, taken right after the timed
+    region (later phases overwrite the static outputs and the .grad tensors).  A list is written flat, its tensors in order; an array of
+    more than DUMP_MAX_ELEMS elements as the elements at a fixed set of indices (seed 0, ascending), the same in every run."""
+    arrays = {}
+    for name, t in outputs.items():
+        if isinstance(t, (list, tuple)):
+            t = torch.cat([c.detach().reshape(-1).float() for c in t])
+        a = torch.as_tensor(t).detach().float().cpu()
+        if a.numel() > DUMP_MAX_ELEMS:
+            a = a.reshape(-1)[dump_sample_indices(a.numel())]
+        arrays[name] = a.numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs, more than the {DUMP_MAX_BYTES} allowed")
+    return arrays
+
+
+def write_outputs(path, arrays):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def step_outputs(coach, loss_dict):
+    """What one mapper step hands its caller: the loss terms it returns, the mapper gradients it computed and the mapper parameters
+    its optimizer step wrote."""
+    params = list(coach.net.mapper.parameters())
+    out = {k: v for k, v in loss_dict.items() if torch.is_tensor(v) or isinstance(v, (int, float))}
+    out["mapper_grads"] = [p.grad if p.grad is not None else torch.zeros_like(p) for p in params]
+    out["mapper_params"] = params
+    return host_arrays(out)
+
+
+def training_state(coach):
+    """The mapper parameters, the optimizer state and the step count, copied (see restore_training_state)."""
+    import copy
+    return ([p.detach().clone() for p in coach.net.mapper.parameters()], copy.deepcopy(coach.optimizer.state_dict()), coach.global_step)
+
+
+def restore_training_state(coach, state):
+    """Put back what training_state() copied, in place (a captured step keeps the parameters' addresses): the stabilisation loop runs
+    as many training steps as the clocks need, and without this the state the timed steps start from would depend on that count."""
+    params, opt, step = state
+    with torch.no_grad():
+        for p, s in zip(coach.net.mapper.parameters(), params):
+            p.copy_(s)
+    coach.optimizer.load_state_dict(opt)
+    coach.global_step = step
 
 
 def pmc_traffic():
@@ -358,10 +424,11 @@ def build_config5(device, batch, rank):
     return imgs, e4e, g, clip, net, text, att
 
 
-def measure_config5(args, rank, world, device, batch):
+def measure_config5(args, rank, world, device, batch, dump=False):
     """BASELINE configs[4] on this rank's share of the images: 256^2 image -> e4e -> S codes -> features -> region-attention
     net (mask + new codes) -> masked 1024^2 generator -> CLIP features (where2edit_amd.demo_pipeline.invert_and_edit).
-    Inference: every rank works on its own images, nothing is exchanged.  Random-init weights of the real architectures."""
+    Inference: every rank works on its own images, nothing is exchanged.  Random-init weights of the real architectures.
+    `dump`: the result also holds the last timed call's outputs as host arrays (`outputs`)."""
     from where2edit_amd.demo_pipeline import invert_and_edit
     imgs, e4e, g, clip, net, text, att = build_config5(device, batch, rank)
 
@@ -395,6 +462,7 @@ def measure_config5(args, rank, world, device, batch):
         out = step()
     barrier()
     dt = time.perf_counter() - t0
+    outputs = host_arrays(out) if dump else None
     if world > 1:
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -403,6 +471,7 @@ def measure_config5(args, rank, world, device, batch):
     if not finite:
         raise SystemExit("non-finite output")
     return {"value": batch * world * args.steps / dt, "unit": "images/s", "ms_per_step": 1e3 * dt / args.steps, "batch": batch,
+            "outputs": outputs,
             "workload": f"BASELINE configs[4]: e4e encode -> S codes -> 26 features -> region-attention net (cluster-pooled mask, new codes) -> "
                         f"masked FFHQ-1024 generator -> CLIP features (show_demo/try_demo.py:93-157), batch {batch}/GPU, no backward",
             "stabilise_steps": n_stab, "stabilised": ok, "mask_mean": float(out["mask"].mean()), "hip_graph": use_graph,
@@ -410,11 +479,13 @@ def measure_config5(args, rank, world, device, batch):
 
 
 def bench_config5(args, rank, world, device):
-    r = measure_config5(args, rank, world, device, args.batch)
+    r = measure_config5(args, rank, world, device, args.batch, dump=bool(args.dump_outputs) and rank == 0)
     if world > 1:
         torch.distributed.destroy_process_group()
     if rank != 0:
         return
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, r["outputs"])
     print(json.dumps({
         "metric": "1024^2 edited images/sec, invert-and-edit inference pipeline (BASELINE configs[4])", "value": r["value"],
         "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": r["ms_per_step"],
@@ -435,19 +506,25 @@ def main():
                     help="latents per GPU (weak scaling).  Default: 4 at --gpus 1 (BASELINE configs[1]), 8 at --gpus N > 1 "
                          "(configs[3]: 64 latents over 8 GPUs)")
     ap.add_argument("--size", type=int, default=1024)
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline as well: the per-kernel roofline, the bf16x3 and fp16-CLIP previews, "
+                         "n1_b8, config3, config5, the CPU baseline and (N > 1) n1_equal_batch; the --no-* switches below drop parts of "
+                         "it.  Without it a run only sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--timing-stride", type=int, default=4,
                     help="the roofline's HIP events are recorded on every N-th timed step (166 timed event records per step "
                          "cost the step 5 %%: 159 images/s without them, 150 with them on every step)")
-    ap.add_argument("--no-preview", action="store_true", help="skip the extra K steps in the opt-in bf16x3 conv precision (N=1 only)")
+    ap.add_argument("--no-preview", action="store_true", help="--full: skip the extra K steps in the opt-in bf16x3 conv precision (N=1 only)")
     ap.add_argument("--side-stream", action="store_true",
                     help="inside the graph, fork the no-grad G(w) pass onto a second stream (+1-2 %% images/s; off by default: "
                          "overlapped kernels stretch each other's durations, so a rocprofv3 trace of the run would no longer "
                          "show the per-kernel times the roofline is quoted on)")
-    ap.add_argument("--no-n1-b8", action="store_true", help="skip the extra batch-8 measurement (`n1_b8`) of a default N=1 run")
-    ap.add_argument("--no-config3", action="store_true", help="skip the extra BASELINE configs[2] measurement of a default N=1 run")
-    ap.add_argument("--no-config5", action="store_true", help="skip the extra BASELINE configs[4] measurement (batch 4 = 32 images / 8 GPUs) of a default N=1 run")
+    ap.add_argument("--no-n1-b8", action="store_true", help="skip the extra batch-8 measurement (`n1_b8`) of a --full N=1 run")
+    ap.add_argument("--no-config3", action="store_true", help="skip the extra BASELINE configs[2] measurement of a --full N=1 run")
+    ap.add_argument("--no-config5", action="store_true", help="skip the extra BASELINE configs[4] measurement (batch 4 = 32 images / 8 GPUs) of a --full N=1 run")
     ap.add_argument("--graph", default="auto", choices=["auto", "on", "off"], nargs="?", const="on",
                     help="replay the step as one captured hipGraph (Coach.capture_step) instead of ~330 eager launches; the per-kernel "
                          "HIP-event roofline is then taken from eager steps run right after the timed region (same kernels, same "
@@ -477,7 +554,7 @@ def main():
                          "step (Coach.accumulated_step) -- SURVEY 8(d) cfg4 asks for both curves")
     ap.add_argument("--global-batch", type=int, default=64, help="--scaling strong: latents per step over all GPUs")
     ap.add_argument("--no-n1-reference", action="store_true",
-                    help="N > 1: skip the K extra steps WITHOUT the gradient all-reduce that give the line its one-GPU figure at "
+                    help="N > 1 with --full: skip the K extra steps WITHOUT the gradient all-reduce that give the line its one-GPU figure at "
                          "the same per-GPU batch (`n1_equal_batch`)")
     ap.add_argument("--lib-option", action="append", default=[], metavar="NAME=VALUE",
                     help="w2e_set_option(NAME, VALUE) before the run -- for same-box A/Bs of a kernel switch inside the real step (e.g. "
@@ -490,6 +567,9 @@ def main():
                          "stand-in step (2 ms sleep + the all-reduce of a 12.6 MB bucket of host memory).  The line it prints says so "
                          "and carries no value")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline alone
+        args.no_cpu_baseline = args.no_kernel_timing = args.no_preview = args.no_n1_b8 = args.no_config3 = args.no_config5 = True
+        args.no_n1_reference = True
     if args.batch is None:
         args.batch = 4 if (args.gpus == 1 and args.scaling == "weak") else 8
     if args.scaling == "strong":
@@ -554,18 +634,23 @@ def main():
             graph_note = f"eager: capture failed ({type(e).__name__}: {e})"[:300]
             torch.cuda.synchronize()
     args.graph = use_graph
+    state0 = training_state(coach)
     stab_steps, stab_ok = (0, False) if args.no_stabilise else stabilise(step_fn, world=world, device=device)
+    restore_training_state(coach, state0)
     for _ in range(args.warmup):
         step_fn()
     barrier()
     timer = None if args.no_kernel_timing else profiling.KernelTimer()
     sampled = 0
+    dumped = None
     if args.graph:  # the timed region is graph replays only; the per-kernel roofline comes from eager steps after it
         t0 = time.perf_counter()
         for i in range(args.steps):
             last = step_fn()
         barrier()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:  # (before the eager steps below change the parameters)
+            dumped = step_outputs(coach, last)
         if timer is not None:
             timer.__enter__()
             for i in range(max(1, args.steps // args.timing_stride)):
@@ -586,6 +671,8 @@ def main():
         dt = time.perf_counter() - t0
         if timer is not None:
             timer.__exit__(None, None, None)
+        if args.dump_outputs and rank == 0:
+            dumped = step_outputs(coach, last)
     n1_ref = None
     if world > 1:
         t = torch.tensor([dt], device=device, dtype=torch.float64)
@@ -621,6 +708,8 @@ def main():
     loss = float(last["loss"])
     if not (loss == loss):
         raise SystemExit("loss is NaN")
+    if dumped is not None:
+        write_outputs(args.dump_outputs, dumped)
     global_batch = per_gpu * world
     value = global_batch * args.steps / dt
     out = {
@@ -803,6 +892,7 @@ def main():
         coach = coach3 = None
         torch.cuda.empty_cache()
         out["config5"] = measure_config5(args, rank, world, device, 4)
+        del out["config5"]["outputs"]
         out["config5"]["same_as"] = "`bench.py --workload 5 --batch 4`"
         torch.cuda.empty_cache()
     if world == 1 and not args.no_cpu_baseline:

@@ -292,6 +292,52 @@ def test_bench_refuses_tuning_variables():
     assert r.returncode != 0 and "W2E_TUNE_SKIP" in (r.stderr + r.stdout)
 
 
+def test_bench_dump_arrays_are_float32_sampled_the_same_way_and_capped(tmp_path):
+    """bench.py --dump-outputs: lists are written flat, an output larger than DUMP_MAX_ELEMS as the same seeded sample in every run,
+    everything as float32 .npy files, and more than DUMP_MAX_BYTES in all is refused rather than written."""
+    import numpy as np
+    import bench
+    big = torch.arange(bench.DUMP_MAX_ELEMS + 1000, dtype=torch.float64)
+    a = bench.host_arrays({"img": big, "codes": [torch.ones(3, 4), torch.zeros(5)], "loss": torch.tensor(1.5), "n": 2})
+    assert {k: (v.shape, v.dtype) for k, v in a.items()} == {"img": ((bench.DUMP_MAX_ELEMS,), np.float32), "codes": ((17,), np.float32),
+                                                             "loss": ((), np.float32), "n": ((), np.float32)}
+    assert np.all(np.diff(a["img"]) > 0)  # distinct elements, in index order
+    bench.dump_sample_indices.cache_clear()
+    assert np.array_equal(bench.host_arrays({"img": big})["img"], a["img"])
+    bench.write_outputs(str(tmp_path / "d"), a)
+    assert sorted(os.listdir(tmp_path / "d")) == ["codes.npy", "img.npy", "loss.npy", "n.npy"]
+    assert np.load(tmp_path / "d" / "loss.npy") == np.float32(1.5)
+    with pytest.raises(SystemExit, match="more than"):
+        bench.host_arrays({f"x{i}": big for i in range(5)})
+
+
+def test_bench_puts_back_the_mapper_state_the_stabilisation_loop_trained():
+    """bench.py restores the mapper parameters, the optimizer state and the step count after its stabilisation loop, in place: the
+    step after the restore computes exactly what the first step from the initial state computes."""
+    import bench
+    from where2edit_amd.ranger import Ranger
+    torch.manual_seed(0)
+    mapper = torch.nn.Sequential(torch.nn.Linear(8, 8), torch.nn.Linear(8, 8))
+    coach = types.SimpleNamespace(net=types.SimpleNamespace(mapper=mapper), optimizer=Ranger(mapper.parameters(), lr=0.5), global_step=0)
+    x = torch.randn(4, 8)
+
+    def step():
+        coach.optimizer.zero_grad()
+        mapper(x).square().mean().backward()
+        coach.optimizer.step()
+        coach.global_step += 1
+        return [p.detach().clone() for p in mapper.parameters()]
+
+    ptrs = [p.data_ptr() for p in mapper.parameters()]
+    state = bench.training_state(coach)
+    first = step()
+    for _ in range(7):  # past the look-ahead interval (k = 6)
+        step()
+    bench.restore_training_state(coach, state)
+    assert coach.global_step == 0 and len(coach.optimizer.state) == 0 and [p.data_ptr() for p in mapper.parameters()] == ptrs
+    assert all(torch.equal(a, b) for a, b in zip(step(), first))
+
+
 def test_fused_winograd_kernel_keeps_its_hand_counted_waits():
     """The fused Winograd kernel's transform waves stage their patches with inline-asm `buffer_load_dwordx4 ... lds` and wait for them
     with HAND-WRITTEN `s_waitcnt vmcnt(6)` (csrc/winograd.hip: six DMA instructions per wave and chunk, the newest chunk may fly).

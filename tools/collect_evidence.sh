@@ -3,7 +3,8 @@
 # Raw rocprofv3 output goes to /tmp (the kernel traces are tens of MB); only the stats CSVs and summaries come back.
 #   usage: bash tools/collect_evidence.sh [tag]        (writes gpurun_out/ev_<tag>/)
 set -e
-cd $GRAFT_REPO_ROOT
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+cd "$ROOT"
 export TMPDIR=/tmp
 #   usage: bash tools/collect_evidence.sh [tag] [part]     part 1 = bench lines + micro-benches, 2 = rocprofv3 passes + probes (a gpurun call is
 #   limited to 20 minutes: the two parts are two calls), default both
@@ -13,10 +14,10 @@ O=$GRAFT_REPO_ROOT/gpurun_out/ev_$TAG
 R=/tmp/w2e_prof_$TAG
 rm -rf $R; mkdir -p $O $R
 if [ "$PART" != "2" ]; then
-SECONDS=0; timeout -k 10 400 python3 bench.py > $O/bench_line.json 2> $O/bench_line.err; echo "default bench.py run: $SECONDS s wall" > $O/bench_line_wall.txt
+SECONDS=0; timeout -k 10 400 python3 bench.py --full > $O/bench_line.json 2> $O/bench_line.err; echo "default bench.py run: $SECONDS s wall" > $O/bench_line_wall.txt
 echo bench done
-timeout -k 10 300 python3 bench.py --workload 3 --batch 8 --no-cpu-baseline --no-preview --no-config3 --no-config5 --no-n1-b8 > $O/bench_line_w3_b8.json 2> $O/bench_line_w3_b8.err || true
-timeout -k 10 300 python3 bench.py --workload 2 --batch 8 --no-cpu-baseline --no-preview --no-config3 --no-config5 --no-n1-b8 > $O/bench_line_w2_b8.json 2> $O/bench_line_w2_b8.err || true
+timeout -k 10 300 python3 bench.py --full --workload 3 --batch 8 --no-cpu-baseline --no-preview --no-config3 --no-config5 --no-n1-b8 > $O/bench_line_w3_b8.json 2> $O/bench_line_w3_b8.err || true
+timeout -k 10 300 python3 bench.py --full --workload 2 --batch 8 --no-cpu-baseline --no-preview --no-config3 --no-config5 --no-n1-b8 > $O/bench_line_w2_b8.json 2> $O/bench_line_w2_b8.err || true
 echo config-3 done
 timeout -k 10 200 python3 tools/layer_bench.py --warm 1.5 --iters 50 > $O/layer_bench.txt 2>&1 || true
 timeout -k 10 200 python3 tools/layer_bench.py --batch 8 --warm 1.0 --iters 30 > $O/layer_bench_b8.txt 2>&1 || true
@@ -27,11 +28,11 @@ echo micro done
 fi
 if [ "$PART" = "1" ]; then exit 0; fi
 cd /tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $R/stats -o stats --output-format csv -- python3 $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 3 --no-preview --no-config3 --no-config5 --no-n1-b8 --no-cpu-baseline > $O/bench_stats.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $R/stats -o stats --output-format csv -- python3 "$ROOT"/bench.py --full --steps 10 --warmup 3 --no-preview --no-config3 --no-config5 --no-n1-b8 --no-cpu-baseline > $O/bench_stats.log 2>&1
 cp $(find $R/stats -name '*kernel_stats.csv' | head -1) $O/kernel_stats.csv
 python3 $GRAFT_REPO_ROOT/tools/prof_summary.py $O/kernel_stats.csv auto > $O/kernel_stats_summary.txt
 echo stats done
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $R/stats3 -o stats --output-format csv -- python3 $GRAFT_REPO_ROOT/bench.py --workload 3 --batch 8 --steps 10 --warmup 3 --no-preview --no-config3 --no-config5 --no-n1-b8 --no-cpu-baseline > $O/bench_stats_w3.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $R/stats3 -o stats --output-format csv -- python3 "$ROOT"/bench.py --full --workload 3 --batch 8 --steps 10 --warmup 3 --no-preview --no-config3 --no-config5 --no-n1-b8 --no-cpu-baseline > $O/bench_stats_w3.log 2>&1
 cp $(find $R/stats3 -name '*kernel_stats.csv' | head -1) $O/kernel_stats_w3_b8.csv
 python3 $GRAFT_REPO_ROOT/tools/prof_summary.py $O/kernel_stats_w3_b8.csv auto > $O/kernel_stats_w3_b8_summary.txt
 echo stats3 done
@@ -70,8 +71,8 @@ echo extras done
 # round 5: the strong-scaling mode at N = 1 (global batch 64 as 8 micro-batches of 8), the 4-rank launcher run on this one GPU (gloo; a GPU box
 # allows 6 processes on its card -- the 8-rank control flow is rehearsed without GPU work by `bench.py --gpus 8 --rehearse`, tests/test_dist_cpu.py),
 # the same A/B of the fused kernel's two round-5 switches
-timeout -k 10 300 python3 bench.py --scaling strong --no-cpu-baseline > $O/bench_line_strong_n1.json 2> $O/bench_line_strong_n1.err || true
-timeout -k 10 400 python3 bench.py --gpus 4 --dist-backend gloo --batch 1 --steps 3 --warmup 2 > $O/bench_line_gloo4.json 2> $O/bench_line_gloo4.err || true
+timeout -k 10 300 python3 bench.py --full --scaling strong --no-cpu-baseline > $O/bench_line_strong_n1.json 2> $O/bench_line_strong_n1.err || true
+timeout -k 10 400 python3 bench.py --full --gpus 4 --dist-backend gloo --batch 1 --steps 3 --warmup 2 > $O/bench_line_gloo4.json 2> $O/bench_line_gloo4.err || true
 timeout -k 10 120 python3 bench.py --gpus 8 --rehearse --steps 5 --warmup 2 > $O/bench_rehearse8.json 2> $O/bench_rehearse8.err || true
 for sw in "W2E_TUNE_MW=4 W2E_TUNE_XCD=0" "W2E_TUNE_MW=4" ""; do
 echo "== ${sw:-default (64-channel workgroups, XCD-contiguous blocks)}, batch 8" >> $O/fused_ab.txt
