@@ -46,7 +46,8 @@ const char* w2e_last_error(void);
  *   "deterministic"  [W2E_DETERMINISTIC]   "1": bit-reproducible results -- no fp32 atomics anywhere (no split-K,
  *                                          ordered reductions), the counterpart of the reference's
  *                                          cudnn.deterministic=True (attention/run_attention.py:903-904)
- *   "tune_cfg" [W2E_TUNE_CFG] "<cfg>[,<splits>[,<mode>]]" force a conv tile (tests, tools/layer_bench.py); "" = off
+ *   "tune_cfg" [W2E_TUNE_CFG] "<cfg>[,<splits>[,<mode>]]" force a conv tile (tests, tools/layer_bench.py); "" = off.  A forced
+ *   tile passes the selection's own feasibility filters (LDS, patch slots): one that does not fit a launch fails it
  *   "tune_upall", "tune_dma", "tune_fuse", "tune_print", "tune_blur", "tune_gemm_s": kernel-selection aids -- they
  *   choose between kernels / tiles that compute the same result ("tune_blur": only bit 8, keep the LDS-tile FIR kernels
  *   for wide images; its bits 1/2/4 and "tune_skip" / "tune_clock" drop loads, arithmetic or stores, or synchronise,

@@ -26,6 +26,29 @@ def assert_close(a, b, tol, what=""):
     assert e <= tol, f"{what}: rel err {e:.3e} > {tol:.1e}"
 
 
+def plane_errors(y, ref, absref):
+    """[B,C] of max|y - ref| / max(absref) over each (sample, channel) plane.  `absref` holds the scale of the terms that were summed
+    into each output (e.g. the same float64 convolution run on |x| and |w|), so that a plane of small outputs is judged by its own
+    arithmetic and not by the largest value of the whole tensor, as rel_err does."""
+    y, ref, absref = (torch.as_tensor(t).double().cpu() for t in (y, ref, absref))
+    assert y.shape == ref.shape == absref.shape, (y.shape, ref.shape, absref.shape)
+    b, c = y.shape[:2]
+    err = (y - ref).abs().reshape(b, c, -1).amax(2)
+    return err / absref.abs().reshape(b, c, -1).amax(2).clamp_min(1e-30)
+
+
+def assert_close_planes(y, ref, absref, tol, what=""):
+    """Every (sample, channel) plane within `tol` of `ref`, relative to the plane's own term scale (plane_errors).  Used beside
+    assert_close, never instead of it.  Returns the worst plane's error."""
+    e = plane_errors(y, ref, absref)
+    if e.numel() == 0:
+        return 0.0
+    worst = int(e.argmax())
+    b, c = divmod(worst, e.shape[1])
+    assert e[b, c] <= tol, f"{what}: plane (sample {b}, channel {c}) rel err {float(e[b, c]):.3e} > {tol:.1e}"
+    return float(e[b, c])
+
+
 GRAD_ERRORS = []  # (what, max-norm relative error, cosine, tolerance) of every assert_grad_close call: printed at the end of the run (conftest)
 
 GRAD_TOL = 1e-3  # BASELINE.json:north_star's relative fp32 tolerance, applied to end-to-end gradients too

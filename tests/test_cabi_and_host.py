@@ -389,3 +389,26 @@ def test_fused_winograd_kernel_keeps_its_hand_counted_waits():
                 i = group[-1] + 1
             else:
                 i += 1
+
+
+def test_plane_error_metric_sees_a_wrong_small_channel():
+    """helpers.assert_close_planes judges each (sample, channel) plane against the scale of the terms summed into it: an error of
+    1e-3 of a low-magnitude output channel hides below 1e-4 of the global max-norm (assert_close passes) and is caught per plane."""
+    import torch.nn.functional as F
+    from helpers import assert_close, assert_close_planes
+    g = torch.Generator().manual_seed(5)
+    k, n = 12, 16
+    x = torch.randn(2, k, 9, 11, generator=g, dtype=torch.float64) * torch.exp(1.5 * torch.randn(k, generator=g, dtype=torch.float64))[None, :, None, None]
+    wt = torch.randn(n, k, 3, 3, generator=g, dtype=torch.float64)
+    wt = wt / wt.flatten(1).norm(dim=1)[:, None, None, None] * torch.exp(1.5 * torch.randn(n, generator=g, dtype=torch.float64))[:, None, None, None]
+    ref = F.conv2d(x, wt, padding=1)
+    absref = F.conv2d(x.abs(), wt.abs(), padding=1)
+    plane_max = ref.abs().amax((2, 3))
+    b, c = divmod(int(plane_max.argmin()), n)
+    assert plane_max[b, c] * 1e-3 < 1e-4 * ref.abs().max(), "the heavy-tailed reference has no low-magnitude plane"
+    y = ref.clone()
+    y[b, c, 4, 5] += 1e-3 * plane_max[b, c]  # one wrong value in the smallest plane
+    assert_close(y, ref, 1e-4, "global max-norm")
+    assert_close_planes(ref, ref, absref, 1e-12, "unperturbed")
+    with pytest.raises(AssertionError, match=rf"plane \(sample {b}, channel {c}\)"):
+        assert_close_planes(y, ref, absref, 1e-4, "per plane")

@@ -1190,21 +1190,33 @@ static int conv_impl(int mode, const float* x, const float* wp, const float* in_
         const int tw6 = wp2 < 32 ? wp2 : 32, th6 = 64 / tw6 > 0 ? 64 / tw6 : 1;
         if ((int64_t)batch * ceil_div(n_ch, 64) * ceil_div(h, th6) * ceil_div(w, tw6) >= 256) sp_max = 1;
     }
-    for (int c = 0; c < ncfg; ++c) {
-        const int tn = 32 * cfgs[c].nob * cfgs[c].wo, tm = 32 * cfgs[c].npb * cfgs[c].wp;
+    // Whether tile c (all_phase: its all-phase UP form) fits this launch: the LDS budget, the register-prefetch slots per thread and
+    // DOWN's slot cap.  The selection loops and a tile forced by tune_cfg both pass through it (a forced tile beyond these limits
+    // would stage only part of its patch).
+    auto tile_fits = [&](int c, bool all_phase) {
+        const int tn = 32 * cfgs[c].nob * cfgs[c].wo, tm = 32 * (all_phase ? cfgs[c].npb / 4 : cfgs[c].npb) * cfgs[c].wp;
         const int tw = wp2 < 32 ? wp2 : ((wp2 >= 64 && tm >= 256) ? 64 : 32);
         const int th = tm / tw;
-        if (th < 1) continue;
+        if (th < 1) return false;
         const int ph = mode == W2E_CONV_SAME ? th + 2 : (up ? th + 1 : 2 * th + 1);
         const int pw = mode == W2E_CONV_SAME ? tw + 2 : (up ? tw + 1 : 2 * tw + 1);
         const int nt = 64 * cfgs[c].wo * cfgs[c].wp;
+        const int slots = max_patch_slots(mode, tm, nt);
+        if (all_phase) return sizeof(float) * ((size_t)kc * 9 * tn + (size_t)kc * ph * pw) <= 150 * 1024 && ph * pw <= nt * slots;
         // deepest K-chunk of this tile (UP: light phases go 16 deep unless the register budget forbids it)
-        const int kdeep = (up && cfgs[c].nob * cfgs[c].npb < 8 && max_patch_slots(mode, tm, nt) <= 2) ? 16 : kc;
+        const int kdeep = (up && cfgs[c].nob * cfgs[c].npb < 8 && slots <= 2) ? 16 : kc;
         const size_t lds_c = up ? sizeof(float) * ((size_t)32 * tn + (size_t)kdeep * ph * pw)
                                 : sizeof(float) * ((size_t)kc * 9 * tn + (size_t)kc * ph * pw);
-        if (lds_c > 150 * 1024) continue;
-        if (mode == W2E_CONV_DOWN && max_patch_slots(mode, tm, nt) > 5) continue;  // prefetch registers: 8 channels x slots
-        if (ph * pw > nt * max_patch_slots(mode, tm, nt)) continue;  // register-prefetch slots per thread
+        if (lds_c > 150 * 1024) return false;
+        if (mode == W2E_CONV_DOWN && slots > 5) return false;  // prefetch registers: 8 channels x slots
+        return ph * pw <= nt * slots;  // register-prefetch slots per thread
+    };
+    for (int c = 0; c < ncfg; ++c) {
+        if (!tile_fits(c, false)) continue;
+        const int tn = 32 * cfgs[c].nob * cfgs[c].wo, tm = 32 * cfgs[c].npb * cfgs[c].wp;
+        const int tw = wp2 < 32 ? wp2 : ((wp2 >= 64 && tm >= 256) ? 64 : 32);
+        const int th = tm / tw;
+        const int nt = 64 * cfgs[c].wo * cfgs[c].wp;
         const double tiles = (double)batch * ceil_div(n_ch, tn) * ceil_div(h, th) * ceil_div(w, tw);
         const double waves_per_simd = nt / 256.0;
         const double unit = (double)cfgs[c].nob * cfgs[c].npb * waves_per_simd * (k_ch / 2.0) * 64.0;  // one tap
@@ -1243,14 +1255,11 @@ static int conv_impl(int mode, const float* x, const float* wp, const float* in_
         double best_a_cost = 0.0;
         for (int ci = 0; ci < 6 && tune_all != 0; ++ci) {
             const int c = kAll[ci];
+            if (!tile_fits(c, true)) continue;
             const int tn = 32 * cfgs[c].nob * cfgs[c].wo, tm = 32 * (cfgs[c].npb / 4) * cfgs[c].wp;
             const int tw = wp2 < 32 ? wp2 : ((wp2 >= 64 && tm >= 256) ? 64 : 32);
             const int th = tm / tw;
-            if (th < 1) continue;
-            const int ph = th + 1, pw = tw + 1;
             const int nt = 64 * cfgs[c].wo * cfgs[c].wp;
-            if (sizeof(float) * ((size_t)kc * 9 * tn + (size_t)kc * ph * pw) > 150 * 1024) continue;
-            if (ph * pw > nt * max_patch_slots(W2E_CONV_UP, tm, nt)) continue;
             const double tiles = (double)batch * ceil_div(n_ch, tn) * ceil_div(h, th) * ceil_div(w, tw);
             const double unit = (double)cfgs[c].nob * (cfgs[c].npb / 4) * (nt / 256.0) * (k_ch / 2.0) * 64.0;  // one tap
             const double t_stage = (double)ceil_div(k_ch, kc) * 1200.0;
@@ -1280,7 +1289,11 @@ static int conv_impl(int mode, const float* x, const float* wp, const float* in_
 #endif
     if (opt.tune_cfg >= 0) {  // tests / tools/layer_bench.py: "<cfg>[,<splits>[,<mode>]]", third field: only launches of that mode
         const int fc = opt.tune_cfg, fs = opt.tune_cfg_splits, fm = opt.tune_cfg_mode;
-        if (fc < (use_all ? kNumCfgAll : ncfg) && (fm < 0 || fm == mode)) best = fc, best_splits = fs > 0 ? fs : 1;
+        if (fc < (use_all ? kNumCfgAll : ncfg) && (fm < 0 || fm == mode)) {
+            W2E_REQUIRE(tile_fits(fc, use_all), "modconv3x3: tile %d (forced by tune_cfg) does not fit mode %d%s, K %d N %d %dx%d (LDS budget / patch slots)",
+                        fc, mode, use_all ? " (all-phase)" : "", k_ch, n_ch, h, w);
+            best = fc, best_splits = fs > 0 ? fs : 1;
+        }
     }
     if (opt.deterministic) best_splits = 1;  // no fp32 atomics onto y: one workgroup owns every output element
     if (opt.tune_print) fprintf(stderr, "modconv mode %d%s K %d N %d %dx%d B %d -> cfg %d splits %d\n", mode, use_all ? " (all-phase)" : "", k_ch, n_ch, h, w, batch, best, best_splits);
@@ -1353,6 +1366,12 @@ static int conv_impl(int mode, const float* x, const float* wp, const float* in_
     const int k_gran = use_all ? kc : kc_max;
     p.k_per = (int)(ceil_div(ceil_div(k_ch, best_splits), k_gran) * k_gran);
     p.splits = (int)ceil_div(k_ch, p.k_per);
+    if (opt.tune_print) {  // the variant that runs (tests/test_gpu_conv_variants.py keys its coverage census on this line); a split
+                           // activation / bias + PReLU runs as the plain kernel followed by an elementwise pass ("act_pass" / "prelu_pass")
+        const char* epi = prelu ? (p.splits > 1 ? "prelu_pass" : "prelu") : act ? (p.splits > 1 ? "act_pass" : "act") : dot_with ? "dot" : "plain";
+        fprintf(stderr, "modconv variant mode %d all %d cfg %d splits %d dma %d x3 %d epi %s\n", mode, use_all ? 1 : 0, best, p.splits,
+                use_dma ? 1 : 0, use_x3 ? 1 : 0, epi);
+    }
     if (up) {
         // border units (one wave each): image x 32-channel block x 32-position block of the last row (W+1 positions) / column (H)
         p.groups_row = (int)ceil_div(w + 1, 32), p.groups_col = (int)ceil_div(h, 32);

@@ -104,7 +104,7 @@ __global__ __launch_bounds__(64 * (MW + 4), 1) void wino4_fused3_kernel(const fl
     constexpr int PQ = 8 * PR * QR;       // quads of one patch chunk (1440 for both shapes)
     static_assert(PR * PC == 720 && PQ <= 24 * 64, "patch geometry");
     constexpr int PS = 24 * 64 * 4;       // floats of one ring stage: 24 wave-instructions x 64 lanes x 16 B (>= PQ quads)
-    // LDS byte map (the launch passes the same sum as its dynamic size): V 0 .. 73 728, ring .. 147 456, tables .. 151 936.  The ring
+    // LDS byte map (the launch passes the same sum as its dynamic size): V 0 .. 73 728, ring .. 147 456, tables (sctab 512 + etab 704 floats) .. 152 320.  The ring
     // starts ABOVE 64 KB: the M0 base of `buffer_load ... lds` must carry byte offsets up to 147 455, which gfx950 (160 KB of LDS per
     // CU) does and earlier parts with a 16-bit field do not -- an ISA change here has to fail the build, not the numbers.
     static_assert(2 * VS * 4 == 73728 && (2 * VS + 3 * PS) * 4 == 147456, "fused Winograd kernel: LDS map of the V stages and the DMA ring");
@@ -490,6 +490,9 @@ int w2e_wino_fused(const float* x, const float* in_scale, const float* uf, const
     const size_t lds3 = (size_t)(2 * 36 * 2 * 32 * 4 + 3 * 24 * 64 * 4 + 2 * 256 + 704) * 4;
     static unsigned done3[4][4];  // [epilogue][block shape x matrix waves]
     const bool wide = (w & 63) == 0 && !((wgs >> 16) & 16);  // blocks of 64 x 8 pixels (bit 4 of a tuning build's mask: keep 32 x 16)
+    if (options().tune_print)  // the variant that runs (tests/test_gpu_conv_variants.py keys its coverage census on this line)
+        fprintf(stderr, "wino_fused variant act %d dot %d txn %d mw %d xmap %d grid %dx%d blocks %lld K %d N %d %dx%d B %d\n", act, dot_with ? 1 : 0,
+                wide ? 16 : 8, mw8 ? 8 : 4, xmap, gx, nby, (long long)blocks, k_ch, n_ch, h, w, batch);
 #define W2E_WF3_(ACTv, DOTv, TXNv, MWv, slot, sub)                                                                                          \
     do {                                                                                                                                   \
         W2E_REQUIRE(big_lds_once((const void*)wino4_fused3_kernel<ACTv, DOTv, TXNv, MWv>, &done3[slot][sub]), "wino_fused: cannot enable %zu B of LDS", lds3); \

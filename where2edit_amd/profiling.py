@@ -1,5 +1,10 @@
 """HIP-event timing of individual C-ABI calls on the stream they are launched on (torch's current
-stream).  bench.py uses it to price the dominant kernel inside the timed region; off by default."""
+stream).  bench.py uses it to price the dominant kernel inside the timed region; off by default.
+conv_selections(): which conv kernel variant every launch of a piece of work picked."""
+import os
+import sys
+import tempfile
+
 import torch
 
 _active = None
@@ -47,3 +52,33 @@ class _Span:
 def span(name, work=0.0):
     """Returns an object whose .end() closes the span, or None when timing is off."""
     return _Span(name, work) if (_active is not None and _active.enabled) else None
+
+
+SELECTION_PREFIXES = ("modconv mode", "modconv variant", "wino_fused variant", "  ")
+
+
+def conv_selections(fn):
+    """Runs fn() once with the library's `tune_print` option on and returns (lines, wino): `lines` = what w2e_modconv3x3 /
+    w2e_conv3x3 / w2e_wino_fused printed to stderr, in launch order ("modconv mode ..." with its "  lds-dma ..." / "  bf16x3 ..."
+    lines, "modconv variant ...", "wino_fused variant ..."), `wino` = the lines of the Winograd forms chosen on the Python side
+    (functional.WINO_LOG).  tools/cfg_selections.py and the coverage census in tests/test_gpu_conv_variants.py both use it."""
+    from . import _lib
+    from . import functional as K
+    torch.cuda.synchronize()
+    sys.stderr.flush()
+    with tempfile.TemporaryFile(mode="w+b") as tmp:
+        saved = os.dup(2)
+        os.dup2(tmp.fileno(), 2)  # the library prints with fprintf(stderr)
+        try:
+            _lib.set_option("tune_print", 1)
+            K.WINO_LOG = []
+            fn()
+            torch.cuda.synchronize()
+        finally:
+            _lib.set_option("tune_print", 0)
+            wino, K.WINO_LOG = K.WINO_LOG, None
+            os.dup2(saved, 2)
+            os.close(saved)
+        tmp.seek(0)
+        lines = [ln for ln in tmp.read().decode().splitlines() if ln.startswith(SELECTION_PREFIXES)]
+    return lines, wino
