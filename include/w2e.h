@@ -36,7 +36,8 @@ extern "C" {
 
 /* 5: additive over 4 -- w2e_pack_kq_h / w2e_gemm_pk_h / w2e_gemm_pk_h_splits (w2e_vit.h), the options tune_xcd / tune_mw; no existing
  * signature changed */
-#define W2E_VERSION 5
+/* 6: additive over 5 -- w2e_maxpool2x2_fwd / w2e_maxpool2x2_relu_bwd / w2e_mse_relu_fwd (w2e_irse.h, the VGG16 perceptual loss) */
+#define W2E_VERSION 6
 
 int w2e_version(void);
 const char* w2e_last_error(void);

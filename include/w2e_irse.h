@@ -1,6 +1,7 @@
-/* w2e_irse.h -- C ABI of the kernels behind the ArcFace IR-SE50 identity loss (criteria/id_loss.py:7-40,
- * models/facial_recognition/model_irse.py:9-48, helpers.py:56-119) and the e4e encoder that shares its body
- * (models/encoders/psp_encoders.py:124-200) in libw2e.so (gfx950).
+/* w2e_irse.h -- C ABI of the kernels behind the frozen CNN critics: IR-SE50 and the VGG16 perceptual loss.  The ArcFace
+ * IR-SE50 identity loss (criteria/id_loss.py:7-40, models/facial_recognition/model_irse.py:9-48, helpers.py:56-119), the e4e
+ * encoder that shares its body (models/encoders/psp_encoders.py:124-200) and the VGG16 relu2_2 perceptual loss
+ * (criteria/perceptual_loss.py) in libw2e.so (gfx950).
  *
  * The network runs in eval mode (id_loss.py:14): BatchNorm is a per-channel affine map (a = gamma/sqrt(var+eps),
  * b = beta - mean*a) that the host folds into the convolutions' scales / bias; PReLU rides in the conv epilogue.
@@ -34,7 +35,8 @@ int w2e_conv3x3(int mode, const float* x, const float* wp, const float* in_scale
  * the convolution because the padding is applied after it.) */
 int w2e_affine_act_fwd(const float* x, const float* a, const float* b, const float* slope, float* y, int batch, int channels,
                        int64_t hw, void* stream);
-/* gx = a[c] * gy * (y > 0 ? 1 : slope[c])   (y = the forward OUTPUT; valid for slope > 0, where sign(y) = sign(pre)).
+/* gx = a[c] * gy * (y > 0 ? 1 : slope[c])   (y = the forward OUTPUT; valid for slope >= 0: for slope > 0
+ * sign(y) = sign(pre), and for slope = 0 (ReLU) y > 0 is exactly pre > 0).
  * planar != 0: gy is the phase-planar T of W2E_CONV_UP ([B,C,2,2,h/2+1,WP]), `planar` = the row pitch WP the caller allocated it
  * with (must equal W2E_PLANAR_PITCH(width/2): a mismatch is refused instead of read past), and the element read for (yy,xx) is
  * T[yy+1][xx+1] -- the crop that turns the adjoint of DOWN into the gradient of the padded stride-2 convolution;
@@ -72,6 +74,27 @@ int w2e_shortcut_add_bwd(float* gx, const float* g, int batch, int channels, int
 /* FPN merge of the pSp / e4e encoders (models/encoders/helpers.py:123-140): out [planes,oh,ow] = bilinear up-sampling of
  * x [planes,ih,iw] (align_corners = True) + y [planes,oh,ow].  Forward only (the encoders are inference networks here). */
 int w2e_upsample_add(const float* x, const float* y, float* out, int64_t planes, int ih, int iw, int oh, int ow, void* stream);
+
+/* ---- VGG16 perceptual loss (criteria/perceptual_loss.py): the 3x3 convolutions are w2e_conv3x3 (bias + a zero slope = ReLU),
+ * the ReLU backward between two convolutions is w2e_affine_act_bwd with a zero slope. */
+
+/* MaxPool2d(2, 2) over [planes,height,width] -> [planes,height/2,width/2] (floored, like PyTorch).  Ties and NaN follow PyTorch's
+ * max_pool2d: the first maximum in row-major window order wins, a NaN in the window propagates.  height, width >= 2. */
+int w2e_maxpool2x2_fwd(const float* x, float* y, int64_t planes, int height, int width, void* stream);
+/* Its backward, the arg-max recomputed from the saved pool INPUT y [planes,height,width] (no index tensor):
+ *   gx = [relu != 0: y > 0] * (position is its window's first arg-max ? g : 0),   g [planes,height/2,width/2];
+ * the row / column dropped by flooring get 0.  relu != 0 folds the backward of the ReLU that produced y (y = relu(pre)). */
+int w2e_maxpool2x2_relu_bwd(const float* g, const float* y, float* gx, int64_t planes, int height, int width, int relu, void* stream);
+
+/* Size of the partials slab w2e_mse_relu_fwd reduces through (floats the caller allocates, at least). */
+#define W2E_MSE_PARTIALS 1024
+/* The MSE head on two feature maps (nn.MSELoss(), mean over every element): f1 [batch, per_sample], f2 [batch2, per_sample] with
+ * batch2 = batch or 1 (broadcast over the batch);  loss[0] = sum (f1 - f2)^2 / N,  N = batch * per_sample.
+ * gpre1 (optional, [batch, per_sample]) = (2/N) (f1 - f2) [f1 > 0]: the gradient with the ReLU mask of f1's own ReLU folded in;
+ * gpre2 (optional, batch2 = batch only) = -(2/N) (f1 - f2) [f2 > 0], the same for f2.  Bit-reproducible: per-workgroup partials
+ * into `partials` (n_partials >= W2E_MSE_PARTIALS floats, checked), then one fixed-order sum; no atomics. */
+int w2e_mse_relu_fwd(const float* f1, const float* f2, int batch, int batch2, int64_t per_sample, float* gpre1, float* gpre2,
+                     float* partials, int n_partials, float* loss, void* stream);
 
 #ifdef __cplusplus
 }

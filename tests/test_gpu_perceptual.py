@@ -1,0 +1,326 @@
+"""The VGG16 perceptual loss (criteria/perceptual_loss.py) on the HIP kernels: 2x2 max-pooling forward / fused pool + ReLU
+backward / the MSE head against PyTorch and float64, Vgg16 and PerceptualLoss against the float64 restatement of
+test_perceptual_host.py and the reference's fixture (tests/golden/perceptual.npz), and one region-attention trainer step with
+the perceptual term against the oracle composition."""
+import types
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+import make_golden_perceptual as P
+import seeded
+from helpers import assert_close, assert_grad_close, golden
+from test_perceptual_host import ref_activations, ref_loss, ref_preprocess_matrix, ref_vgg
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+
+
+def _vgg():
+    from where2edit_amd.perceptual_loss import Vgg16
+    vgg = Vgg16()
+    vgg.load_state_dict(P.vgg_state_dict(), strict=True)
+    return vgg.to(DEV)
+
+
+def _loss(size):
+    from where2edit_amd.perceptual_loss import PerceptualLoss
+    return PerceptualLoss(types.SimpleNamespace(stylegan_size=size), model=_vgg())
+
+
+def _hip_activations(vgg, x, slices=2):
+    """{conv index: post-ReLU activation} of the HIP forward (the `route` of ref_vgg)."""
+    from where2edit_amd import perceptual_loss as PL
+    plan, acts, h = vgg.plan(), {}, x
+    with torch.no_grad():
+        for k in range(slices):
+            for i in PL.SLICES[k]:
+                if i in PL.POOLS:
+                    h = PL._maxpool(h)
+                elif i in PL.CONVS:
+                    h = acts[i] = PL._conv_relu(plan, i, h)
+    return {i: a.cpu() for i, a in acts.items()}
+
+
+def _discrete_differences(route, own):
+    """(ReLU signs, pool windows) where the HIP forward decides differently from the float64 evaluation's own forward."""
+    flips = sum(int(((route[i] > 0) != (own[i] > 0)).sum()) for i in route)
+    windows = 0
+    for i in route:
+        if i in (2, 7, 14):
+            _, a = F.max_pool2d(route[i].double(), 2, 2, return_indices=True)
+            _, b = F.max_pool2d(own[i], 2, 2, return_indices=True)
+            windows += int((a != b).sum())
+    return flips, windows
+
+
+# ---------------------------------------------------------------------------------------------- kernels
+def _tie_input(shape, key):
+    """Small integers: many exact ties; some all-zero windows; values around 0 for the ReLU."""
+    x = torch.round(seeded.tensor(key, shape, 1.2)).clamp(-2, 2)
+    x[..., :2, :2] = 0.0
+    return x
+
+
+@pytest.mark.parametrize("shape", [(3, 5, 7, 9), (2, 67, 17, 20), (1, 3, 16, 16), (2, 3, 6, 10)])
+def test_maxpool_forward_equals_torch(shape):
+    from where2edit_amd.perceptual_loss import _maxpool
+    x = _tie_input(shape, f"mp.fwd{shape}")
+    x[0, 0, 2, 3] = float("nan")  # a NaN propagates (window (1, 1))
+    y = _maxpool(x.to(DEV)).cpu()
+    ref = F.max_pool2d(x, 2, 2)
+    assert y.shape == ref.shape and torch.isnan(y[0, 0, 1, 1])
+    torch.testing.assert_close(y, ref, rtol=0, atol=0, equal_nan=True)
+
+
+@pytest.mark.parametrize("shape", [(3, 5, 7, 9), (2, 67, 17, 20), (1, 3, 16, 16), (2, 3, 6, 10)])
+def test_fused_pool_relu_backward_equals_float64_autograd(shape):
+    from where2edit_amd.perceptual_loss import _maxpool_bwd
+    x = _tie_input(shape, f"mp.bwd{shape}").double()
+    x[0, 0, 0:2, 2:4] = torch.tensor([[2.0, 2.0], [2.0, 1.0]], dtype=torch.float64)  # a positive exact tie: window (0, 1)
+    b, c, h, w = shape
+    g = seeded.tensor(f"mp.g{shape}", (b, c, h // 2, w // 2))
+    xr = x.clone().requires_grad_(True)
+    (ref,) = torch.autograd.grad((F.max_pool2d(F.relu(xr), 2, 2) * g.double()).sum(), xr)
+    y = F.relu(x).float()  # the saved pool input (post-ReLU)
+    got = _maxpool_bwd(g.to(DEV), y.to(DEV), relu=True).cpu()
+    assert torch.equal(got.double(), ref)
+    assert got[0, 0, 0, 2] == g[0, 0, 0, 1] and got[0, 0, 0, 3] == 0 and got[0, 0, 1, 2] == 0  # the first arg-max takes it
+    if h % 2:
+        assert not got[:, :, -1].any()
+    if w % 2:
+        assert not got[:, :, :, -1].any()
+    # relu=False: the pool's own adjoint (Vgg16's slice boundary), against autograd of max_pool2d alone
+    yr = y.double().requires_grad_(True)
+    (ref0,) = torch.autograd.grad((F.max_pool2d(yr, 2, 2) * g.double()).sum(), yr)
+    assert torch.equal(_maxpool_bwd(g.to(DEV), y.to(DEV), relu=False).cpu().double(), ref0)
+
+
+def _head(f1, f2, grad2=False):
+    from where2edit_amd import irse_hip as IR
+    from where2edit_amd._lib import call, ptr, stream_ptr
+    b1, b2, per = f1.shape[0], f2.shape[0], f1[0].numel()
+    g = torch.empty(((2 if grad2 else 1) * b1,) + tuple(f1.shape[1:]), device=DEV)
+    part = torch.empty(IR.MSE_PARTIALS, device=DEV)
+    loss = torch.empty((), device=DEV)
+    call("w2e_mse_relu_fwd", ptr(f1), ptr(f2), b1, b2, per, ptr(g[:b1]), ptr(g[b1:]) if grad2 else None, ptr(part), IR.MSE_PARTIALS,
+         ptr(loss), stream_ptr())
+    return loss.cpu(), g.cpu()
+
+
+@pytest.mark.parametrize("shape", [(4, 128, 112, 112), (3, 7, 5, 9)])
+def test_loss_head_matches_float64_and_is_bit_reproducible(shape):
+    f1 = seeded.tensor(f"head.f1{shape}", shape)
+    f2 = seeded.tensor(f"head.f2{shape}", (1,) + shape[1:])
+    f2r = f2.expand(shape).contiguous()
+    n = f1.numel()
+    d = f1.double() - f2r.double()
+    ref = (d ** 2).mean()
+    loss, g = _head(f1.to(DEV), f2.to(DEV))
+    assert abs(loss.double() - ref) <= 1e-6 * ref
+    gref = (2.0 / n) * d * (f1 > 0).double()
+    torch.testing.assert_close(g.double(), gref, rtol=1e-6, atol=1e-30)
+    # the broadcast target equals the repeated one (bit for bit: same values, same reduction order); two calls are identical
+    loss_r, g_r = _head(f1.to(DEV), f2r.to(DEV))
+    assert torch.equal(loss_r, loss) and torch.equal(g_r, g)
+    loss2, g2 = _head(f1.to(DEV), f2.to(DEV))
+    assert torch.equal(loss2, loss) and torch.equal(g2, g)
+    # both sides' gradients (equal batches)
+    loss3, g3 = _head(f1.to(DEV), f2r.to(DEV), grad2=True)
+    torch.testing.assert_close(g3[shape[0]:].double(), -(2.0 / n) * d * (f2r > 0).double(), rtol=1e-6, atol=1e-30)
+    assert torch.equal(loss3, loss)
+
+
+# ---------------------------------------------------------------------------------------------- Vgg16
+@pytest.mark.parametrize("wino", ["auto", False])
+@pytest.mark.parametrize("shape", [(2, 3, 224, 224), (1, 3, 70, 90)])
+def test_vgg16_forward_matches_float64(shape, wino):
+    from where2edit_amd import functional as K
+    vgg = _vgg()
+    x = torch.tanh(seeded.tensor(f"vgg.x{shape}", shape, 0.8))
+    K.set_winograd(wino)
+    try:
+        with torch.no_grad():
+            out = vgg(x.to(DEV))
+    finally:
+        K.set_winograd("auto")
+    ref = ref_vgg(P.vgg_state_dict(), x.double())
+    for name, o, r in zip(out._fields, out, ref):
+        assert o.shape == r.shape, name
+        assert_close(o, r, 1e-4, f"{name} {shape} winograd {wino}")
+
+
+def test_vgg16_matches_the_reference_fixture_with_input_gradients():
+    g = golden("perceptual")
+    vgg = _vgg()
+    x, r = P.vgg_inputs()
+    xg = x.to(DEV).requires_grad_(True)
+    out = vgg(xg)
+    for name in out._fields:
+        assert_close(getattr(out, name), g["vgg." + name], 1e-4, name)
+    (gx,) = torch.autograd.grad((out.relu2_2 * r.to(DEV)).sum(), xg)
+    assert_grad_close(gx, g["vgg.grad"], "Vgg16 input gradient vs the reference fixture")
+
+
+def test_vgg16_input_gradient_through_all_slices():
+    """d (sum_k <relu_k, r_k>) / dX at 70x90 (odd sizes at every pool) against float64 with the HIP forward's discrete decisions."""
+    vgg = _vgg()
+    x = torch.tanh(seeded.tensor("vgg.gx", (1, 3, 70, 90), 0.8))
+    xg = x.to(DEV).requires_grad_(True)
+    out = vgg(xg)
+    rs = [seeded.tensor(f"vgg.gr{k}", tuple(o.shape)) for k, o in enumerate(out)]
+    (gx,) = torch.autograd.grad(sum((o * r.to(DEV)).sum() for o, r in zip(out, rs)), xg)
+    route = _hip_activations(vgg, x.to(DEV), slices=4)
+    xd = x.double().requires_grad_(True)
+    ref = ref_vgg(P.vgg_state_dict(), xd, route=route)
+    (gref,) = torch.autograd.grad(sum((o * r.double()).sum() for o, r in zip(ref, rs)), xd)
+    flips, windows = _discrete_differences(route, ref_activations(P.vgg_state_dict(), x.double(), slices=4))
+    print(f"Vgg16 70x90: {flips} ReLU signs, {windows} pool windows differ from float64's own forward")
+    assert_grad_close(gx, gref, "Vgg16 input gradient, 4 slices, 70x90")
+
+
+# ---------------------------------------------------------------------------------------------- PerceptualLoss
+@pytest.mark.parametrize("size", [256, 1024])
+@pytest.mark.parametrize("batch", [1, 2, 4])
+def test_perceptual_loss_matches_float64(size, batch):
+    from where2edit_amd import functional as K
+    loss_mod = _loss(size)
+    img1 = torch.tanh(seeded.tensor(f"pl.img1.{size}", (batch, 3, size, size), 0.8))
+    target = torch.tanh(seeded.tensor(f"pl.img2.{size}", (1, 3, size, size), 0.8))
+    x1 = img1.to(DEV).requires_grad_(True)
+    loss = loss_mod(x1, target.to(DEV))
+    (g1,) = torch.autograd.grad(loss, x1)
+    # the float64 oracle takes the HIP forward's discrete decisions (ReLU signs, pool1 routing): loss.model(pre) gives relu1_2
+    with torch.no_grad():
+        pre = torch.cat([K.clip_preprocess(x1.detach()), K.clip_preprocess(target.to(DEV)).expand(batch, -1, -1, -1)])
+        route = _hip_activations(loss_mod.model, pre)
+        assert torch.equal(route[2], loss_mod.model(pre).relu1_2.cpu())
+    sd = P.vgg_state_dict()
+    xd = img1.double().requires_grad_(True)
+    ref = ref_loss(sd, xd, target.double(), size, route=route)
+    (gref,) = torch.autograd.grad(ref, xd)
+    own = ref_activations(sd, ref_preprocess_matrix(torch.cat([img1, target.expand(batch, -1, -1, -1)]).double(), size))
+    flips, windows = _discrete_differences(route, own)
+    print(f"PerceptualLoss {size}^2 batch {batch}: loss {loss.item():.6e} (float64 {ref.item():.6e}); {flips} ReLU signs, "
+          f"{windows} pool1 windows differ from float64's own forward")
+    assert windows <= 64 and flips <= 4096
+    assert abs(loss.item() - ref.item()) <= 1e-4 * abs(ref.item())
+    assert_grad_close(g1, gref, f"PerceptualLoss input gradient {size}^2 batch {batch}")
+
+
+def test_perceptual_loss_matches_the_reference_fixture():
+    g = golden("perceptual")
+    loss_mod = _loss(P.SIZE)
+    img1, target = P.loss_inputs()
+    x1 = img1.to(DEV).requires_grad_(True)
+    loss = loss_mod(x1, target.to(DEV))
+    (g1,) = torch.autograd.grad(loss, x1)
+    assert abs(loss.item() - float(g["loss.value"])) <= 1e-4 * abs(float(g["loss.value"]))
+    pos = P.grad_positions(g1.numel())
+    # The fixture is the reference's fp32 CPU gradient, with its own discrete decisions: 3 relu1_1 pre-activations within rounding of
+    # 0 take another sign there than in float64, which moves that gradient 4.4e-3 (max-norm) from float64's own
+    # (test_perceptual_host.py routes them).  Measured here: 1.35e-3 against the fixture, 3e-6 against the routed float64 (above).
+    assert_grad_close(g1.reshape(-1)[pos.to(DEV)], g["loss.grad_at"], "PerceptualLoss gradient vs the reference fixture (sampled)",
+                      tol=5e-3)
+    # the repeated target gives the broadcast one's value; a target that requires grad gets its gradient (equal batches)
+    t = target.to(DEV).repeat(P.LOSS_BATCH, 1, 1, 1).requires_grad_(True)
+    loss_r = loss_mod(x1, t)
+    g1r, gt = torch.autograd.grad(loss_r, [x1, t])
+    assert abs(loss_r.item() - loss.item()) <= 1e-6 * loss.item()
+    xd, td = img1.double().requires_grad_(True), target.double().repeat(P.LOSS_BATCH, 1, 1, 1).requires_grad_(True)
+    _, gtd = torch.autograd.grad(ref_loss(P.vgg_state_dict(), xd, td, P.SIZE), [xd, td])
+    assert_grad_close(gt, gtd, "PerceptualLoss target gradient")
+    with pytest.raises(RuntimeError, match="broadcast"):
+        loss_mod(x1, target.to(DEV).requires_grad_(True))
+
+
+def test_perceptual_loss_is_bit_reproducible_in_deterministic_mode():
+    import where2edit_amd
+    loss_mod = _loss(1024)
+    img1 = torch.tanh(seeded.tensor("pl.det", (2, 3, 1024, 1024), 0.8)).to(DEV)
+    target = torch.tanh(seeded.tensor("pl.det_t", (1, 3, 1024, 1024), 0.8)).to(DEV)
+    runs = []
+    where2edit_amd.set_deterministic(True)
+    try:
+        for _ in range(2):
+            x1 = img1.clone().requires_grad_(True)
+            loss = loss_mod(x1, target)
+            (g1,) = torch.autograd.grad(loss, x1)
+            runs.append((loss.detach().clone(), g1))
+    finally:
+        where2edit_amd.set_deterministic(False)
+    assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1])
+
+
+def test_perceptual_loss_other_sizes_take_the_literal_chain():
+    loss_mod = _loss(256)
+    img1 = torch.tanh(seeded.tensor("pl.lit", (1, 3, 128, 128), 0.8))
+    target = torch.tanh(seeded.tensor("pl.lit_t", (1, 3, 128, 128), 0.8))
+    x1 = img1.to(DEV).requires_grad_(True)
+    with pytest.warns(UserWarning, match="literal"):
+        loss = loss_mod(x1, target.to(DEV))
+    (g1,) = torch.autograd.grad(loss, x1)
+    sd = P.vgg_state_dict()
+    pre = lambda t: F.avg_pool2d(F.interpolate(t, scale_factor=7, mode="nearest"), 8)  # noqa: E731  (128*7/8 = 112^2)
+    route = _hip_activations(loss_mod.model, torch.cat([pre(x1.detach()), pre(target.to(DEV))]))
+    xd = img1.double().requires_grad_(True)
+    f = ref_vgg(sd, torch.cat([pre(xd), pre(target.double())]), 2, route)[1]
+    ref = ((f[:1] - f[1:]) ** 2).mean()
+    (gref,) = torch.autograd.grad(ref, xd)
+    assert abs(loss.item() - ref.item()) <= 1e-4 * abs(ref.item())
+    assert_grad_close(g1, gref, "PerceptualLoss input gradient, literal chain")
+
+
+# ---------------------------------------------------------------------------------------------- trainer
+def test_region_attention_trainer_step_with_the_perceptual_term():
+    """test_region_attention_trainer_step_matches_oracle with the reference's identity term (run_attention.py:1007, :1277, :1288,
+    :1415): loss_total += ramp2 * 0.1 * PerceptualLoss(img_gen, first_img), the oracle's term in float64."""
+    import make_golden_attention as M
+    from oracle import attention_net as OA
+    from oracle import clip_model as OC
+    from oracle import ops as OO
+    from oracle import stylegan2 as OG
+    from test_gpu_attention import _trainer
+    from where2edit_amd.run_attention import RegionAttentionTrainer
+    size, b = 256, 2
+    tr0, gsd, csd, msd, edim = _trainer(size)
+    with pytest.raises(ValueError, match="not both"):
+        RegionAttentionTrainer(tr0.g_ema, tr0.clip_loss, tr0.mapper, identity_loss=_loss(size), perceptual_loss=_loss(size), device=DEV)
+    tr = RegionAttentionTrainer(tr0.g_ema, tr0.clip_loss, tr0.mapper, attention_layer=M.ATT_LAYER, lr=0.01, steps=100, device=DEV,
+                                perceptual_loss=_loss(size))
+    tr.global_step = 30  # t = 0.3: ramp2 = 1
+    w1 = seeded.wplus_latents(b, OG.n_latent(size), salt=51)
+    w2 = seeded.wplus_latents(b, OG.n_latent(size), salt=52)
+    att_text = seeded.tensor("trainer.att_text", (b, edim), 0.3)
+    names = [n for n, p in tr.mapper.named_parameters() if p.requires_grad]
+    osd = {k: v.clone() for k, v in msd.items()}
+    for n in names:
+        osd[n].requires_grad_(True)
+    with torch.no_grad():
+        img1, _, _, _ = OG.generator_forward(gsd, [w1], size=size, input_is_latent=True, randomize_noise=False, return_features=True)
+        cfo = OC.encode_image(csd, OO.clip_preprocess(img1, size))
+        img2, _, codes2, feats2 = OG.generator_forward(gsd, [w2], size=size, input_is_latent=True, randomize_noise=False, return_features=True)
+        feats2 = list(feats2) + [gsd["input.input"].repeat(b, 1, 1, 1)]
+        first_feats = [f[:1].repeat(b, 1, 1, 1) for f in feats2]
+        first_codes = [s[:1].repeat(b, 1, 1, 1, 1) for s in codes2]
+        first_img = img2[:1]
+    x = [torch.cat([cfo.unsqueeze(1), s[:, :, :, 0, 0]], -1) for s in first_codes]
+    first_text = att_text[:1].repeat(b, 1)
+    new_codes, amap, dl, _ = OA.forward(osd, x, first_feats, M.SIZE, attention_text=first_text, attention_layer=M.ATT_LAYER,
+                                        cluster_layer=M.CLUSTER_LAYER, clusters=M.CLUSTERS, latent_dim=edim)
+    img_gen, _ = OG.generator_forward(gsd, [new_codes], size=size, input_is_stylespace=True, randomize_noise=False,
+                                      attention_layer=M.ATT_LAYER, attention_map=amap, feature_map=first_feats)
+    feat_gen = OC.encode_image(csd, OO.clip_preprocess(img_gen, size))
+    l_consist = OA.info_nce(feat_gen, cfo)
+    l_perc = ref_loss(P.vgg_state_dict(), img_gen.double(), first_img.double(), size)
+    total_o = l_consist + 1.0 * (0.03 * dl[2] + 0.01 * dl[1].squeeze()) + 0.03 * dl[0] + (1.0 * 0.1 * l_perc).float()
+    grads_o = torch.autograd.grad(total_o, [osd[n] for n in names], allow_unused=True)
+    d = tr.train_step(w1.to(DEV), w2.to(DEV), att_text.to(DEV))
+    for key, ref in (("loss_consist", l_consist), ("loss_delta", dl[0]), ("loss_secphase", dl[1]), ("loss_essence", dl[2]),
+                     ("loss_identity", l_perc), ("loss", total_o)):
+        assert abs(float(d[key]) - float(ref.detach())) <= 2e-4 * max(abs(float(ref.detach())), 1e-3), (key, float(d[key]), float(ref.detach()))
+    params = dict(tr.mapper.named_parameters())
+    used = [(n, g) for n, g in zip(names, grads_o) if g is not None]
+    assert_grad_close(torch.cat([params[n].grad.reshape(-1).cpu() for n, _ in used]), torch.cat([g.reshape(-1).double() for _, g in used]),
+                      "trainable mapper parameters with the perceptual term")

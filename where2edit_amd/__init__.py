@@ -10,6 +10,8 @@ Layout:
   attention_model.py      attention/attention_model.py Generator (features + region blend)
   latent_mappers.py, styleclip_mapper.py   mapper/ surface
   clip_vit.py, clip_loss.py                criteria/clip_loss.py surface + ViT-B/32
+  id_loss.py, irse_hip.py                  criteria/id_loss.py surface + IR-SE50 on the conv engine
+  perceptual_loss.py                       criteria/perceptual_loss.py surface: VGG16 relu2_2 MSE on the conv engine
   coach.py, ranger.py     the mapper training step (mapper/training/coach.py:70-92) + optimizer
   dist.py                 data-parallel step: shard latents, one RCCL all-reduce of mapper grads
 """

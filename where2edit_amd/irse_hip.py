@@ -29,7 +29,12 @@ PROTOS = {
     "w2e_se_apply_bwd": (_I, [_P, _P, _P, _P, _I, _I, _L, _P]),
     "w2e_shortcut_add_bwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "w2e_upsample_add": (_I, [_P, _P, _P, _L, _I, _I, _I, _I, _P]),
+    "w2e_maxpool2x2_fwd": (_I, [_P, _P, _L, _I, _I, _P]),
+    "w2e_maxpool2x2_relu_bwd": (_I, [_P, _P, _P, _L, _I, _I, _I, _P]),
+    "w2e_mse_relu_fwd": (_I, [_P, _P, _I, _I, _L, _P, _P, _P, _I, _P, _P]),
 }
+
+MSE_PARTIALS = 1024  # W2E_MSE_PARTIALS (include/w2e_irse.h): the partials slab of w2e_mse_relu_fwd
 
 
 def declare(lib):

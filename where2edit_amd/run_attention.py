@@ -366,14 +366,18 @@ class RegionAttentionTrainer:
 
     `consistency`: "recompute" (default here) broadcasts rank 0's W+ latent of sample 0 (36 KB) and re-runs the generator
     on it locally; "broadcast" is the reference's pattern (27 feature maps + 26 codes + the image = 542 MB per step from
-    rank 0).  Both give every rank the same tensors.  `identity_loss`: None (lambda_id term off) or a module
-    `(img_gen, img_orig) -> (loss, _)` such as IDLoss -- the reference's VGG perceptual loss needs torchvision weights
-    and is out of scope.  Text prompts: the reference samples phrases and tokenises them with OpenAI's BPE
-    (not in this image); callers pass CLIP text features / token ids."""
+    rank 0).  Both give every rank the same tensors.  The lambda_id term: `perceptual_loss`, a
+    `perceptual_loss.PerceptualLoss` -- the reference's own identity term (:1007, :1277, :1288: loss_identity = the VGG16
+    relu2_2 perceptual loss of img_gen against rank 0's first sample) -- or `identity_loss`, a module `(img_gen, img_orig) ->
+    (loss, _)` such as IDLoss; at most one of the two; with neither the term is off.  Text prompts: the reference samples
+    phrases and tokenises them with OpenAI's BPE (not in this image); callers pass CLIP text features / token ids."""
 
     def __init__(self, g_ema, clip_loss, mapper, *, attention_layer=13, lr=0.01, steps=10000, lambda_ess=0.03, lambda_sec=0.01,
-                 lambda_id=0.1, lambda_delta=0.03, identity_loss=None, consistency="recompute", device="cuda:0", amp=False):
+                 lambda_id=0.1, lambda_delta=0.03, identity_loss=None, consistency="recompute", device="cuda:0", amp=False,
+                 perceptual_loss=None):
         from . import dist as w2e_dist
+        if identity_loss is not None and perceptual_loss is not None:
+            raise ValueError("RegionAttentionTrainer: pass identity_loss or perceptual_loss, not both (both are the lambda_id term)")
         self.device = device
         self.g_ema = g_ema.to(device).eval().requires_grad_(False)
         self.clip_loss = clip_loss.to(device)
@@ -385,6 +389,7 @@ class RegionAttentionTrainer:
         self.lr, self.steps = lr, steps
         self.lambdas = (lambda_ess, lambda_sec, lambda_id, lambda_delta)
         self.identity_loss = identity_loss.to(device) if identity_loss is not None else None
+        self.perceptual_loss = perceptual_loss.to(device) if perceptual_loss is not None else None
         if consistency not in ("recompute", "broadcast"):
             raise ValueError("consistency must be 'recompute' or 'broadcast'")
         self.consistency = consistency
@@ -474,6 +479,11 @@ class RegionAttentionTrainer:
              "loss_delta": loss_delta.detach()}
         if self.identity_loss is not None:
             loss_identity = self.identity_loss(img_gen, first_img)[0]
+            total = total + ramp2 * (l_id * loss_identity)
+            d["loss_identity"] = loss_identity.detach()
+        elif self.perceptual_loss is not None:
+            # :1277, :1288 (first_img is rank 0's sample 0 repeated: its first row is the whole target, broadcast over the batch)
+            loss_identity = self.perceptual_loss(img_gen, first_img[:1])
             total = total + ramp2 * (l_id * loss_identity)
             d["loss_identity"] = loss_identity.detach()
         d["loss"] = total.detach()
