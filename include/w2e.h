@@ -37,7 +37,9 @@ extern "C" {
 /* 5: additive over 4 -- w2e_pack_kq_h / w2e_gemm_pk_h / w2e_gemm_pk_h_splits (w2e_vit.h), the options tune_xcd / tune_mw; no existing
  * signature changed */
 /* 6: additive over 5 -- w2e_maxpool2x2_fwd / w2e_maxpool2x2_relu_bwd / w2e_mse_relu_fwd (w2e_irse.h, the VGG16 perceptual loss) */
-#define W2E_VERSION 6
+/* 7: additive over 6 -- w2e_modconv_wgrad_plan / w2e_modconv_wgrad / w2e_modconv_wgrad_finish / w2e_modconv_wsq (K1d, the conv-weight
+ * gradient of decoder fine-tuning) */
+#define W2E_VERSION 7
 
 int w2e_version(void);
 const char* w2e_last_error(void);
@@ -197,6 +199,31 @@ int w2e_demod_all_fwd(const w2e_demod_layer* layers, int n_layers, int batch, fl
  * s1 - noise_w*s2 - bias[o]*s3.  Exactly one of sums / dz is non-NULL.  gd (optional) receives dz/d. */
 int w2e_demod_bwd(const float* sums, const float* dz, const float* noise_w, const float* bias, const float* d,
                   const float* s, const float* wsq, float* gs, float* gd, int batch, int cin, int cout, void* stream);
+
+/* ---- K1d  conv-weight gradient of ModulatedConv2d (decoder fine-tuning; replaces the weight branch of autograd through
+ * model.py:234-276: `weight = self.scale * self.weight * style`, the demodulation of model.py:241-243 and the grouped
+ * conv2d / conv_transpose2d of model.py:253-274).  Always plain fp32 MFMA: conv_precision does not apply.  No atomics, no
+ * zero-fill, no in-launch counters: bit-reproducible in every mode.
+ *   mode 0 SAME    C[o,i,ky,kx] = sum_{b,y,x} (d*g)[b,o,y,x] * (s*x)[b,i,y+ky-1,x+kx-1]   g [B,cout,h,w]
+ *   mode 1 UP      C[o,i,ky,kx] = sum_{b,y,x} (d*g)[b,o,2y+ky,2x+kx] * (s*x)[b,i,y,x]      g [B,cout,2h+1,2w+1] (the
+ *                  gradient on the transposed-conv grid, i.e. after the adjoint blur; no flip: wmod[n].transpose(0,1))
+ *   mode 2 CENTRE  the (1,1) tap of SAME only (a 1x1 layer)
+ * x [B,cin,h,w], s [B,cin], d [B,cout] or NULL (no demodulation).  `slab` [splits][taps][cout][cin] receives one partial C
+ * per K split (taps = 9, or 1 for CENTRE); every element is written.  `splits` from w2e_modconv_wgrad_plan (any value >= 1
+ * is valid; the plan spreads K over the chip). */
+int w2e_modconv_wgrad_plan(int mode, int batch, int cin, int cout, int h, int w, int* splits);
+int w2e_modconv_wgrad(int mode, const float* g, const float* x, const float* d, const float* s, float* slab, int batch, int cin,
+                      int cout, int h, int w, int splits, void* stream);
+/* dw [cout][cin][taps] (the parameter's [1,cout,cin,k,k]) = scale * sum_split slab (in split order)
+ *                                                       - scale^2 * weight * sum_b c[b,o] * s[b,i]^2,   c = dz * d^2
+ * with dz from `sums` / `dz` exactly as w2e_demod_bwd forms it (one of the two non-NULL).  d == NULL: no demodulation, the
+ * second term is absent (sums, dz, noise_w, bias, weight are then not read). */
+int w2e_modconv_wgrad_finish(const float* slab, int splits, const float* weight, const float* sums, const float* dz,
+                             const float* noise_w, const float* bias, const float* d, const float* s, float* dw, int batch, int cin,
+                             int cout, int taps, float scale, void* stream);
+/* wsq [cout][cin] = sum_t (scale * weight[o][i][t])^2 (model.py:241-242 before the style): the demodulation table of a layer
+ * whose weight is trained, rebuilt every forward without a memset. */
+int w2e_modconv_wsq(const float* weight, float* wsq, int cout, int cin, int taps, float scale, void* stream);
 
 /* All style modulations of one generator pass in one launch (model.py:211, `style = self.modulation(style)` in each of
  * the 26 ModulatedConv2d): every layer's EqualLinear(style_dim, cin_l) -- weight*scale and bias*lr_mul, model.py:151-158

@@ -27,3 +27,10 @@ def set_deterministic(enabled=True):
     from . import _lib
     _lib.set_option("deterministic", 1 if enabled else 0)
     torch.use_deterministic_algorithms(bool(enabled), warn_only=True)
+
+
+def train_conv_weights(module):
+    """Opt-in decoder fine-tuning (stylegan2.train_conv_weights): every ModulatedConv2d weight under `module` requires grad and gets
+    its gradient from the conv-weight-gradient kernels; stylegan2.freeze_conv_weights undoes it."""
+    from .stylegan2 import train_conv_weights as _train
+    return _train(module)

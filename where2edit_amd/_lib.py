@@ -46,6 +46,10 @@ _PROTOS = {
     "w2e_demod_fwd": (_I, [_P, _P, _P, _I, _I, _I, _F, _P]),
     "w2e_demod_all_fwd": (_I, [ctypes.POINTER(DemodLayer), _I, _I, _F, _P]),
     "w2e_demod_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "w2e_modconv_wgrad_plan": (_I, [_I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int)]),
+    "w2e_modconv_wgrad": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "w2e_modconv_wgrad_finish": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
+    "w2e_modconv_wsq": (_I, [_P, _P, _I, _I, _I, _F, _P]),
     "w2e_style_affine_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "w2e_style_affine_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "w2e_torgb_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),

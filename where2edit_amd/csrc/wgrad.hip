@@ -1,0 +1,286 @@
+// K1d: the conv-weight gradient of ModulatedConv2d (decoder fine-tuning), fp32 MFMA for gfx950.
+// Replaces the weight branch of autograd through models/stylegan2/model.py:234-276 (the per-sample weight
+// `self.scale * self.weight * style`, its demodulation and the grouped conv / conv_transpose2d).
+//
+// dW[o,i,k] = scale * C[o,i,k] - scale^2 * W[o,i,k] * sum_b c[b,o] * s[b,i]^2,   c[b,o] = dL/dd[b,o] * d[b,o]^3
+// with C the correlation of the demodulated pre-activation gradient and the modulated input:
+//   SAME    C[o,i,ky,kx] = sum_{b,y,x} (d*g)[b,o,y,x] * (s*x)[b,i,y+ky-1,x+kx-1]     (zero outside the image)
+//   UP      C[o,i,ky,kx] = sum_{b,y,x} (d*g)[b,o,2y+ky,2x+kx] * (s*x)[b,i,y,x]        (g on the (2h+1)^2 transposed-conv grid)
+//   CENTRE  the (1,1) tap of SAME only (the 1x1 layer that runs on the 3x3 engine)
+//
+// w2e_modconv_wgrad: implicit GEMM M = Cout, N = Cin * taps, K = batch * pixels.  A workgroup owns a 32(o) x 32(i) block and
+// every tap, and walks its share of the K axis (a contiguous run of 4x16-pixel tiles: the split).  Per tile the g tile and the
+// x tile with its halo are staged into LDS, pixel-major with the 32 channels fastest ([pixel][33]: conflict-free stores and
+// reads), d[b,o] and s[b,i] applied on the way.  Wave w takes tile row w; per pixel pair one A fragment (UP: one B fragment)
+// feeds the 9 taps' v_mfma_f32_32x32x2_f32, one accumulator tile per tap.  At the end the 4 waves' tiles are summed in LDS in
+// wave order and the block is written to the split's slab [split][tap][Cout][Cin]: every element of every slab is written
+// exactly once, so nothing is zero-filled and nothing is added atomically.
+// w2e_modconv_wgrad_finish: sums the slabs in split order, scales, adds the demodulation term, writes [Cout][Cin][k][k].
+#include "common.h"
+
+namespace w2e {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+namespace {
+
+constexpr int WG_TH = 4;   // tile rows (one per wave)
+constexpr int WG_TW = 16;  // tile columns (8 pixel pairs = 8 K-steps of the 32x32x2 MFMA)
+constexpr int WG_CP = 33;  // LDS pitch of one pixel: 32 channels + 1
+
+template <int MODE>
+struct WgradGeom {
+    static constexpr bool up = MODE == 1;
+    static constexpr int taps = MODE == 2 ? 1 : 9;
+    static constexpr int a_w = up ? 2 * WG_TW + 1 : WG_TW;      // g tile
+    static constexpr int a_h = up ? 2 * WG_TH + 1 : WG_TH;
+    static constexpr int b_w = up ? WG_TW : WG_TW + 2;          // x tile (SAME / CENTRE: with the 1-pixel halo)
+    static constexpr int b_h = up ? WG_TH : WG_TH + 2;
+    static constexpr int a_px = a_w * a_h, b_px = b_w * b_h;
+    static constexpr int lds = (a_px + b_px) * WG_CP;
+    static_assert(lds >= 4 * 1024, "the 4-wave reduction reuses the operand tiles");
+    static_assert(lds * 4 <= 64 * 1024, "static LDS");
+};
+
+struct WgradParams {
+    const float* g;
+    const float* x;
+    const float* d;  // [B,Cout] or NULL (no demodulation: 1)
+    const float* s;  // [B,Cin]
+    float* slab;     // [splits][taps][Cout][Cin]
+    int batch, cin, cout, h, w;  // x: [B,Cin,h,w]
+    int gh, gw;                  // g: [B,Cout,gh,gw]
+    int tiles_y, tiles_x, n_tiles, tiles_per_split;
+};
+
+template <int MODE>
+__global__ __launch_bounds__(256) void modconv_wgrad_kernel(WgradParams p) {
+    using G = WgradGeom<MODE>;
+    __shared__ float lds[G::lds];
+    float* la = lds;
+    float* lb = lds + G::a_px * WG_CP;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int i0 = blockIdx.x * 32, o0 = blockIdx.y * 32, sp = blockIdx.z;
+    const int t_lo = sp * p.tiles_per_split;
+    const int t_hi = min(p.n_tiles, t_lo + p.tiles_per_split);
+    const int l31 = lane & 31, kh = lane >> 5;
+
+    f32x16 acc[G::taps];
+#pragma unroll
+    for (int t = 0; t < G::taps; ++t)
+        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+
+    const int per_img = p.tiles_y * p.tiles_x;
+    for (int tile = t_lo; tile < t_hi; ++tile) {
+        const int b = tile / per_img;
+        const int rem = tile - b * per_img;
+        const int ty = rem / p.tiles_x, tx = rem - (rem / p.tiles_x) * p.tiles_x;
+        const int ay0 = G::up ? 2 * ty * WG_TH : ty * WG_TH, ax0 = G::up ? 2 * tx * WG_TW : tx * WG_TW;
+        const int by0 = G::up ? ty * WG_TH : ty * WG_TH - 1, bx0 = G::up ? tx * WG_TW : tx * WG_TW - 1;
+        __syncthreads();  // (the previous tile's reads are done)
+        for (int e = tid; e < 32 * G::a_px; e += 256) {
+            const int c = e / G::a_px, px = e - c * G::a_px;
+            const int r = px / G::a_w, col = px - r * G::a_w;
+            const int yy = ay0 + r, xx = ax0 + col, o = o0 + c;
+            float v = 0.f;
+            if (o < p.cout && yy < p.gh && xx < p.gw) {
+                v = p.g[(((int64_t)b * p.cout + o) * p.gh + yy) * p.gw + xx];
+                if (p.d) v *= p.d[(int64_t)b * p.cout + o];
+            }
+            la[px * WG_CP + c] = v;
+        }
+        for (int e = tid; e < 32 * G::b_px; e += 256) {
+            const int c = e / G::b_px, px = e - c * G::b_px;
+            const int r = px / G::b_w, col = px - r * G::b_w;
+            const int yy = by0 + r, xx = bx0 + col, i = i0 + c;
+            float v = 0.f;
+            if (i < p.cin && yy >= 0 && yy < p.h && xx >= 0 && xx < p.w)
+                v = p.x[(((int64_t)b * p.cin + i) * p.h + yy) * p.w + xx] * p.s[(int64_t)b * p.cin + i];
+            lb[px * WG_CP + c] = v;
+        }
+        __syncthreads();
+        const int r = wv;  // this wave's tile row
+#pragma unroll 2
+        for (int kk = 0; kk < WG_TW / 2; ++kk) {
+            const int pc = 2 * kk + kh;  // the lane's pixel column (k = lane >> 5 of the MFMA)
+            if constexpr (MODE == 1) {
+                const float bv = lb[(r * WG_TW + pc) * WG_CP + l31];
+#pragma unroll
+                for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+                    for (int kx = 0; kx < 3; ++kx) {
+                        const float av = la[((2 * r + ky) * G::a_w + 2 * pc + kx) * WG_CP + l31];
+                        acc[ky * 3 + kx] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[ky * 3 + kx], 0, 0, 0);
+                    }
+            } else {
+                const float av = la[(r * WG_TW + pc) * WG_CP + l31];
+                if constexpr (MODE == 2) {
+                    const float bv = lb[((r + 1) * G::b_w + pc + 1) * WG_CP + l31];
+                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[0], 0, 0, 0);
+                } else {
+#pragma unroll
+                    for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+                        for (int kx = 0; kx < 3; ++kx) {
+                            const float bv = lb[((r + ky) * G::b_w + pc + kx) * WG_CP + l31];
+                            acc[ky * 3 + kx] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[ky * 3 + kx], 0, 0, 0);
+                        }
+                }
+            }
+        }
+    }
+
+    // the 4 waves' partial tiles -> one, summed in wave order; D layout: col = lane & 31 = i, row = (r&3) + 8(r>>2) + 4(lane>>5) = o
+#pragma unroll
+    for (int t = 0; t < G::taps; ++t) {
+        __syncthreads();
+#pragma unroll
+        for (int rr = 0; rr < 16; ++rr) {
+            const int o = (rr & 3) + 8 * (rr >> 2) + 4 * kh;
+            lds[wv * 1024 + o * 32 + l31] = acc[t][rr];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int e = tid + 256 * q;
+            const int o = o0 + (e >> 5), i = i0 + (e & 31);
+            const float v = ((lds[e] + lds[1024 + e]) + lds[2048 + e]) + lds[3072 + e];
+            if (o < p.cout && i < p.cin) p.slab[(((int64_t)sp * G::taps + t) * p.cout + o) * p.cin + i] = v;
+        }
+    }
+}
+
+// One thread per dW element in slab order ([tap][o][i]); the 4 waves of a block sum interleaved quarters of the splits, joined
+// in wave order through LDS.
+__global__ __launch_bounds__(256) void modconv_wgrad_finish_kernel(const float* __restrict__ slab, int splits,
+                                                                   const float* __restrict__ weight, const float* __restrict__ sums,
+                                                                   const float* __restrict__ dz_in, const float* __restrict__ noise_w,
+                                                                   const float* __restrict__ bias, const float* __restrict__ d,
+                                                                   const float* __restrict__ s, float* __restrict__ dw, int batch,
+                                                                   int cin, int cout, int taps, float scale) {
+    __shared__ float part[4][64];
+    const int j = threadIdx.x & 63, q = threadIdx.x >> 6;
+    const int64_t n = (int64_t)taps * cout * cin;
+    const int64_t e = (int64_t)blockIdx.x * 64 + j;
+    float acc = 0.f;
+    if (e < n)
+        for (int k = q; k < splits; k += 4) acc += slab[(int64_t)k * n + e];
+    part[q][j] = acc;
+    __syncthreads();
+    if (q != 0 || e >= n) return;
+    float c = ((part[0][j] + part[1][j]) + part[2][j]) + part[3][j];
+    const int t = (int)(e / ((int64_t)cout * cin));
+    const int oi = (int)(e - (int64_t)t * cout * cin);
+    const int o = oi / cin, i = oi - (oi / cin) * cin;
+    const int64_t widx = ((int64_t)o * cin + i) * taps + t;
+    float v = scale * c;
+    if (d) {
+        // sum_b c[b,o] s[b,i]^2 with c[b,o] = dz[b,o] d[b,o]^2 (the coefficient of w2e_demod_bwd: dz = d * dL/dd)
+        const float nw = noise_w ? noise_w[0] : 0.f;
+        float m = 0.f;
+        for (int b = 0; b < batch; ++b) {
+            float dz;
+            if (sums) {
+                const float* qs = sums + ((int64_t)b * cout + o) * 3;
+                dz = qs[0] - nw * qs[1] - (bias ? bias[o] : 0.f) * qs[2];
+            } else {
+                dz = dz_in[(int64_t)b * cout + o];
+            }
+            const float dv = d[(int64_t)b * cout + o], sv = s[(int64_t)b * cin + i];
+            m += dz * dv * dv * sv * sv;
+        }
+        v -= scale * scale * weight[widx] * m;
+    }
+    dw[widx] = v;
+}
+
+__global__ __launch_bounds__(256) void modconv_wsq_kernel(const float* __restrict__ weight, float* __restrict__ wsq, int n, int taps,
+                                                          float scale) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    float acc = 0.f;
+    for (int t = 0; t < taps; ++t) {
+        const float v = scale * weight[(int64_t)e * taps + t];
+        acc += v * v;
+    }
+    wsq[e] = acc;
+}
+
+int wgrad_taps(int mode) { return mode == 2 ? 1 : 9; }
+
+}  // namespace
+
+}  // namespace w2e
+
+using namespace w2e;
+
+extern "C" {
+
+int w2e_modconv_wgrad_plan(int mode, int batch, int cin, int cout, int h, int w, int* splits) {
+    W2E_REQUIRE(splits, "modconv_wgrad_plan: null splits");
+    W2E_REQUIRE(mode >= 0 && mode <= 2, "modconv_wgrad_plan: mode %d (0 SAME, 1 UP, 2 CENTRE)", mode);
+    W2E_REQUIRE(batch > 0 && cin > 0 && cout > 0 && h > 0 && w > 0, "modconv_wgrad_plan: bad dims");
+    const int64_t n_tiles = (int64_t)batch * ceil_div(h, WG_TH) * ceil_div(w, WG_TW);
+    W2E_REQUIRE(n_tiles < (1ll << 31), "modconv_wgrad_plan: too many pixel tiles");
+    const int64_t blocks = ceil_div(cin, 32) * ceil_div(cout, 32);
+    const int64_t slab = (int64_t)wgrad_taps(mode) * cin * cout;
+    int64_t sp = ceil_div(4 * (int64_t)cu_count(), blocks);  // ~4 workgroups per CU over the whole grid
+    if (sp > n_tiles) sp = n_tiles;
+    if (sp * slab > (1ll << 24)) sp = (1ll << 24) / slab;  // slabs <= 64 MiB
+    if (sp < 1) sp = 1;
+    const int64_t per = ceil_div(n_tiles, sp);
+    *splits = (int)ceil_div(n_tiles, per);
+    return 0;
+}
+
+int w2e_modconv_wgrad(int mode, const float* g, const float* x, const float* d, const float* s, float* slab, int batch, int cin,
+                      int cout, int h, int w, int splits, void* stream) {
+    W2E_REQUIRE(g && x && s && slab, "modconv_wgrad: null tensor");
+    W2E_REQUIRE(mode >= 0 && mode <= 2, "modconv_wgrad: mode %d (0 SAME, 1 UP, 2 CENTRE)", mode);
+    W2E_REQUIRE(batch > 0 && cin > 0 && cout > 0 && h > 0 && w > 0 && splits > 0 && splits < 65536, "modconv_wgrad: bad dims");
+    const int64_t n_tiles = (int64_t)batch * ceil_div(h, WG_TH) * ceil_div(w, WG_TW);
+    W2E_REQUIRE(n_tiles < (1ll << 31) && ceil_div(cin, 32) < 65536 && ceil_div(cout, 32) < 65536, "modconv_wgrad: too large");
+    WgradParams p{};
+    p.g = g, p.x = x, p.d = d, p.s = s, p.slab = slab;
+    p.batch = batch, p.cin = cin, p.cout = cout, p.h = h, p.w = w;
+    p.gh = mode == 1 ? 2 * h + 1 : h, p.gw = mode == 1 ? 2 * w + 1 : w;
+    p.tiles_y = (int)ceil_div(h, WG_TH), p.tiles_x = (int)ceil_div(w, WG_TW), p.n_tiles = (int)n_tiles;
+    p.tiles_per_split = (int)ceil_div(n_tiles, splits);
+    dim3 grid((unsigned)ceil_div(cin, 32), (unsigned)ceil_div(cout, 32), (unsigned)splits);
+    hipStream_t st = (hipStream_t)stream;
+    if (mode == 0)
+        modconv_wgrad_kernel<0><<<grid, 256, 0, st>>>(p);
+    else if (mode == 1)
+        modconv_wgrad_kernel<1><<<grid, 256, 0, st>>>(p);
+    else
+        modconv_wgrad_kernel<2><<<grid, 256, 0, st>>>(p);
+    W2E_LAUNCH_CHECK("modconv_wgrad");
+    return 0;
+}
+
+int w2e_modconv_wgrad_finish(const float* slab, int splits, const float* weight, const float* sums, const float* dz,
+                             const float* noise_w, const float* bias, const float* d, const float* s, float* dw, int batch, int cin,
+                             int cout, int taps, float scale, void* stream) {
+    W2E_REQUIRE(slab && dw, "modconv_wgrad_finish: null tensor");
+    W2E_REQUIRE(batch > 0 && cin > 0 && cout > 0 && (taps == 1 || taps == 9) && splits > 0, "modconv_wgrad_finish: bad dims");
+    if (d) {
+        W2E_REQUIRE((sums != nullptr) != (dz != nullptr), "modconv_wgrad_finish: give exactly one of sums / dz with d");
+        W2E_REQUIRE(weight && s, "modconv_wgrad_finish: the demodulation term needs weight and s");
+    }
+    const int64_t n = (int64_t)taps * cin * cout;
+    modconv_wgrad_finish_kernel<<<(unsigned)ceil_div(n, 64), 256, 0, (hipStream_t)stream>>>(slab, splits, weight, sums, dz, noise_w, bias,
+                                                                                          d, s, dw, batch, cin, cout, taps, scale);
+    W2E_LAUNCH_CHECK("modconv_wgrad_finish");
+    return 0;
+}
+
+int w2e_modconv_wsq(const float* weight, float* wsq, int cout, int cin, int taps, float scale, void* stream) {
+    W2E_REQUIRE(weight && wsq, "modconv_wsq: null tensor");
+    W2E_REQUIRE(cout > 0 && cin > 0 && taps > 0 && (int64_t)cout * cin < (1ll << 31), "modconv_wsq: bad dims");
+    const int n = cout * cin;
+    modconv_wsq_kernel<<<(unsigned)ceil_div(n, 256), 256, 0, (hipStream_t)stream>>>(weight, wsq, n, taps, scale);
+    W2E_LAUNCH_CHECK("modconv_wsq");
+    return 0;
+}
+
+}  // extern "C"

@@ -466,6 +466,43 @@ def demod_coefficients_all(styles, wsqs, eps=1e-8):
     return out
 
 
+WGRAD_SAME, WGRAD_UP, WGRAD_CENTRE = 0, 1, 2
+
+
+def modconv_wsq(weight, scale):
+    """wsq [Cout,Cin] = sum_k (scale*W[o,i,k])^2 of a [1,Cout,Cin,k,k] weight (w2e_modconv_wsq): a kernel, so that a trained layer
+    can rebuild it in every forward, inside a graph capture too."""
+    cout, cin = weight.shape[1], weight.shape[2]
+    wsq = torch.empty((cout, cin), device=weight.device, dtype=torch.float32)
+    call("w2e_modconv_wsq", ptr(_c(weight.detach())), ptr(wsq), cout, cin, weight.shape[3] * weight.shape[4], float(scale), stream_ptr())
+    return wsq
+
+
+def modconv_wgrad(mode, g, x, d, s, weight, scale, sums=None, dz=None, noise_w=None, bias=None):
+    """dL/dW [1,Cout,Cin,k,k] of a ModulatedConv2d (w2e_modconv_wgrad + w2e_modconv_wgrad_finish).  g: the pre-activation gradient
+    ([B,Cout,h,w]; for WGRAD_UP the one on the (2h+1)x(2w+1) transposed-conv grid); x [B,Cin,h,w]; s [B,Cin]; d [B,Cout] or None
+    (no demodulation); sums / dz: the demodulation-path coefficient exactly as w2e_demod_bwd takes it.  Always plain fp32."""
+    b, cin, h, w = x.shape
+    cout = weight.shape[1]
+    taps = 1 if mode == WGRAD_CENTRE else 9
+    splits = ctypes.c_int(0)
+    call("w2e_modconv_wgrad_plan", mode, b, cin, cout, h, w, ctypes.byref(splits))
+    slab = torch.empty(splits.value * taps * cout * cin, device=x.device, dtype=torch.float32)
+    sp = profiling.span("modconv_wgrad", 2.0 * b * cin * cout * taps * h * w)
+    st = stream_ptr()
+    call("w2e_modconv_wgrad", mode, ptr(_c(g)), ptr(_c(x)), ptr(d), ptr(_c(s)), ptr(slab), b, cin, cout, h, w, splits.value, st)
+    dw = torch.empty(weight.shape, device=x.device, dtype=torch.float32)
+    if d is not None:
+        call("w2e_modconv_wgrad_finish", ptr(slab), splits.value, ptr(_c(weight.detach())), ptr(sums), ptr(dz), ptr(noise_w), ptr(bias),
+             ptr(d), ptr(_c(s)), ptr(dw), b, cin, cout, taps, float(scale), st)
+    else:
+        call("w2e_modconv_wgrad_finish", ptr(slab), splits.value, None, None, None, None, None, None, None, ptr(dw), b, cin, cout, taps,
+             float(scale), st)
+    if sp is not None:
+        sp.end()
+    return dw
+
+
 def planar_pitch(w):
     """W2E_PLANAR_PITCH (include/w2e.h): row pitch of the phase planes of the transposed-conv output for an input w wide."""
     return (w + 1 + 15) & ~15
@@ -511,12 +548,15 @@ class _StyledConv(torch.autograd.Function):
     """Fused StyledConv: out = lrelu(d * conv(Wp, s*x) [blur] + nw*noise + bias) * sqrt2 with
     d = rsqrt(s^2 @ wsq^T + eps) (model.py:234-276, 285-290, op/fused_act.py); with fuse_act=False just
     d * conv(Wp, s*x) [blur] (a bare ModulatedConv2d).  Differentiable in x, s (direct + demodulation paths in one
-    gradient), noise_w, bias.  The conv weight is treated as frozen (no weight gradient is produced -- the decoder is
-    never optimised on this path: coach.py:174-180 optimises net.mapper only)."""
+    gradient), noise_w, bias, and -- when the raw `weight` [1,Cout,Cin,k,k] is given (a layer opted in by
+    stylegan2.train_conv_weights) -- in the conv weight (w2e_modconv_wgrad + _finish; `wscale` = 1/sqrt(Cin*k^2)).  Without it
+    the weight is frozen, as on the mapper path (coach.py:174-180 optimises net.mapper only), and no weight-gradient kernel runs."""
 
     @staticmethod
-    def forward(ctx, x, s, wsq, noise, noise_w, bias, packs, blur_kernel, upsample, fuse_act, link=None, d_pre=None):
-        """`d_pre`: the layer's demodulation vector when the caller already has it (demod_coefficients_all)."""
+    def forward(ctx, x, s, wsq, noise, noise_w, bias, packs, blur_kernel, upsample, fuse_act, link=None, d_pre=None, weight=None,
+                wscale=1.0):
+        """`d_pre`: the layer's demodulation vector when the caller already has it (demod_coefficients_all).  `weight`: the
+        trained raw conv weight (packs and wsq are then derived from it by the caller in this very forward)."""
         x, s = _c(x), _c(s)
         b, cin, h, w = x.shape
         wp_f, wp_b = packs
@@ -534,8 +574,9 @@ class _StyledConv(torch.autograd.Function):
                                      act=((None,) + act) if fuse_act else None)
         else:
             out, _ = _modconv_raw(MODE_SAME, x, wp_f, s, d, h, w, act=act)
-        ctx.save_for_backward(x, s, d, wsq, noise, noise_w, bias, out, wp_b, blur_kernel)
+        ctx.save_for_backward(x, s, d, wsq, noise, noise_w, bias, out, wp_b, blur_kernel, weight)
         ctx.cfg = (upsample, fuse_act)
+        ctx.wscale = float(wscale)
         ctx.link = link  # (an ActLink shared with the consuming ToRGB node, or None)
         ctx.n_skip = _NOGRAD_PREFIX if _NOGRAD_PREFIX < b else 0
         ctx.pool = _GRAD_POOL
@@ -544,7 +585,7 @@ class _StyledConv(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gout):
-        x, s, d, wsq, noise, noise_w, bias, out, wp_b, blur_kernel = ctx.saved_tensors
+        x, s, d, wsq, noise, noise_w, bias, out, wp_b, blur_kernel, weight = ctx.saved_tensors
         upsample, fuse_act = ctx.cfg
         n_skip, full = ctx.n_skip, x.shape[0]
         gout_full = gout
@@ -594,6 +635,12 @@ class _StyledConv(torch.autograd.Function):
             # adjoint of Blur(pad=(1,1)) back onto the (2h+1)x(2w+1) transposed-conv grid, then the
             # stride-2 conv that is the adjoint of conv_transpose2d
             gpre = _upfirdn2d_raw(gpre, blur_kernel, 2 * h + 1, 2 * w + 1, 1, 1, 2, 2, False)
+        g_w = None
+        if weight is not None and ctx.needs_input_grad[12]:
+            # the conv-weight gradient from the same gpre (UP: on the transposed-conv grid), x, s, d and demodulation coefficient
+            wmode = WGRAD_UP if upsample else (WGRAD_CENTRE if weight.shape[-1] == 1 else WGRAD_SAME)
+            g_w = modconv_wgrad(wmode, gpre, x, d, s, weight, ctx.wscale, sums=sums if d is not None and fuse_act else None,
+                                dz=dz, noise_w=noise_w if (fuse_act and noise is not None) else None, bias=bias if fuse_act else None)
         mode = MODE_DOWN if upsample else MODE_SAME
         if _lib.get_option("deterministic") and not (mode == MODE_SAME and _wino_form(gpre, gpre.shape[1], cin, h, w, x)):
             # (both Winograd forms sum the partials of their fused dot in a fixed order: they stay)
@@ -611,16 +658,16 @@ class _StyledConv(torch.autograd.Function):
                  ptr(bias) if fuse_act else None, ptr(d), ptr(s), ptr(wsq), ptr(gs), None, b, cin, cout, stream_ptr())
         if n_skip:
             gx = gx_full
-        return gx, gs_full, None, None, g_nw, g_bias, None, None, None, None, None, None
+        return gx, gs_full, None, None, g_nw, g_bias, None, None, None, None, None, None, g_w, None
 
 
-def styled_conv(x, s, wsq, noise, noise_w, bias, packs, blur_kernel, upsample, link=None, demod=None):
-    return _StyledConv.apply(x, s, wsq, noise, noise_w, bias, packs, blur_kernel, upsample, True, link, demod)
+def styled_conv(x, s, wsq, noise, noise_w, bias, packs, blur_kernel, upsample, link=None, demod=None, weight=None, wscale=1.0):
+    return _StyledConv.apply(x, s, wsq, noise, noise_w, bias, packs, blur_kernel, upsample, True, link, demod, weight, wscale)
 
 
-def modconv(x, s, wsq, packs, blur_kernel, upsample):
+def modconv(x, s, wsq, packs, blur_kernel, upsample, weight=None, wscale=1.0):
     """Bare ModulatedConv2d (3x3): d * conv(Wp, s*x), with the FIR blur for the up-sampling variant."""
-    return _StyledConv.apply(x, s, wsq, None, None, None, packs, blur_kernel, upsample, False)
+    return _StyledConv.apply(x, s, wsq, None, None, None, packs, blur_kernel, upsample, False, None, None, weight, wscale)
 
 
 def modconv_down_plain(x, s, d, wp_f, h, w):

@@ -37,25 +37,44 @@ def invalidate_caches(module):
 
 
 def _trainable_weight(mod):
-    """Refuses a conv weight that autograd expects a gradient for.  The packed-weight kernels (K1) compute none: the path this package
-    accelerates never optimises the decoder (mapper/training/coach.py:174-180 hands only net.mapper's parameters to the optimizer), and a
-    second, stock-op backend inside ModulatedConv2d for that case (rounds 2-3 ran the reference's per-sample-weight grouped convolution on
-    MIOpen here) is exactly the silent fallback this package does not have.  One kernel path, or an error that says what to do."""
+    """True for a conv weight that autograd expects a gradient for on a layer opted in by `train_conv_weights` (its gradient then
+    comes from the K1d kernels, w2e_modconv_wgrad); refuses one that was not opted in.  The path this package accelerates never
+    optimises the decoder (mapper/training/coach.py:174-180 hands only net.mapper's parameters to the optimizer), and a second,
+    stock-op backend inside ModulatedConv2d (rounds 2-3 ran the reference's per-sample-weight grouped convolution on MIOpen here) is
+    exactly the silent fallback this package does not have.  One kernel path, or an error that says what to do."""
     if torch.is_grad_enabled() and mod.weight.requires_grad:
+        if getattr(mod, "_train_weight", False):
+            return True
         raise RuntimeError(
             "where2edit_amd: a ModulatedConv2d weight requires grad (decoder fine-tuning).  The HIP kernels treat the decoder as frozen -- "
-            "as the path they serve does (coach.py:174-180 optimises net.mapper only) -- and produce no conv-weight gradient; there is no "
+            "as the path they serve does (coach.py:174-180 optimises net.mapper only) -- unless asked otherwise; there is no "
             "stock-op fallback.  Call stylegan2.freeze_conv_weights(decoder) (or decoder.requires_grad_(False)); gradients to latents, "
-            "styles, noise strengths and biases are unaffected.")
+            "styles, noise strengths and biases are unaffected; or `train_conv_weights` to fine-tune them.")
     return False
 
 
 def freeze_conv_weights(module):
-    """requires_grad_(False) on exactly the parameters this implementation cannot differentiate: the 3x3 (and generic 1x1)
-    ModulatedConv2d weights consumed through the packed-weight kernels.  Everything else stays as it was."""
+    """requires_grad_(False) on exactly the parameters this implementation differentiates only on request: the 3x3 (and generic 1x1)
+    ModulatedConv2d weights consumed through the packed-weight kernels (and ToRGB's).  Clears the `train_conv_weights` mark.
+    Everything else stays as it was."""
     for m in module.modules():
         if isinstance(m, ModulatedConv2d):
             m.weight.requires_grad_(False)
+            m._train_weight = False
+    return module
+
+
+def train_conv_weights(module):
+    """Opt-in decoder fine-tuning: requires_grad_(True) on every ModulatedConv2d weight under `module` and mark those layers, so that
+    their forward takes the raw weight as an autograd input and their backward computes its gradient (w2e_modconv_wgrad +
+    w2e_modconv_wgrad_finish, plain fp32).  The packed weights, sum_k W^2 and the Winograd-domain weights of a marked layer are
+    derived from the live weight in every forward (no cache: a captured step replays with the weights an optimizer step left).
+    `freeze_conv_weights` undoes it.  Coach, the trainers and load_generator_weights keep the decoder frozen: this is the caller's
+    choice, never a default."""
+    for m in module.modules():
+        if isinstance(m, ModulatedConv2d):
+            m.weight.requires_grad_(True)
+            m._train_weight = True
     return module
 
 
@@ -226,24 +245,40 @@ class ModulatedConv2d(nn.Module):
         return (f"{self.__class__.__name__}({self.in_channel}, {self.out_channel}, {self.kernel_size}, "
                 f"upsample={self.upsample}, downsample={self.downsample})")
 
+    def _live(self):
+        """True for a layer opted in by train_conv_weights whose weight is trained: its derived tensors come from the live weight."""
+        return getattr(self, "_train_weight", False) and self.weight.requires_grad
+
     # ---- frozen-weight derived tensors, rebuilt whenever the parameter changes (in-place updates bump _version)
     def _derived(self):
         w = self.weight
+        if self._live():  # trained: derived in every forward, never from the (data_ptr, _version) cache (graph replays, optimizer steps)
+            return self._derive(w)
         key = (w.data_ptr(), w._version, w.device)
         if self._cache_key != key:
-            with torch.no_grad():
-                w4 = w.detach()[0].to(torch.float32)
-                if self.kernel_size == 1:
-                    w9 = torch.zeros(self.out_channel, self.in_channel, 3, 3, device=w.device)
-                    w9[:, :, 1, 1] = w4[:, :, 0, 0]  # 1x1 on the 3x3 engine (generic Cout; ToRGB has its own kernel)
-                else:
-                    w9 = w4.contiguous()
-                fwd = K.conv_pack(w9, self.scale, transpose=False, flip=False)
-                bwd = K.conv_pack(w9, self.scale, transpose=True, flip=not self.upsample)
-                wsq = (w4 * self.scale).square().sum((2, 3)).contiguous()  # [Cout,Cin]: sum_k (scale*W)^2
-            self._cache = (fwd, bwd, wsq)
+            self._cache = self._derive(w)
             self._cache_key = key
         return self._cache
+
+    def _derive(self, w):
+        live = self._live()
+        with torch.no_grad():
+            w4 = w.detach()[0].to(torch.float32)
+            if self.kernel_size == 1:  # 1x1 on the 3x3 engine as the centre tap (generic Cout; ToRGB has its own kernel)
+                if live:
+                    w9 = F.pad(w4, (1, 1, 1, 1))
+                else:
+                    w9 = torch.zeros(self.out_channel, self.in_channel, 3, 3, device=w.device)
+                    w9[:, :, 1, 1] = w4[:, :, 0, 0]
+            else:
+                w9 = w4.contiguous()
+            fwd = K.conv_pack(w9, self.scale, transpose=False, flip=False)
+            bwd = K.conv_pack(w9, self.scale, transpose=True, flip=not self.upsample)
+            if live:  # a kernel (no memset under capture) in every forward
+                wsq = K.modconv_wsq(w, self.scale)
+            else:
+                wsq = (w4 * self.scale).square().sum((2, 3)).contiguous()  # [Cout,Cin]: sum_k (scale*W)^2
+        return fwd, bwd, wsq
 
     def _style(self, style, batch, input_is_stylespace):
         if not input_is_stylespace:
@@ -255,14 +290,13 @@ class ModulatedConv2d(nn.Module):
             raise NotImplementedError("ModulatedConv2d kernels exist for kernel_size 1 and 3 (the sizes the generator uses)")
         batch, in_channel, height, width = input.shape
         style = self._style(style, batch, input_is_stylespace)
-        if _trainable_weight(self):
-            return _modconv_trainable(self, input, style), style
+        train = _trainable_weight(self)
         s2d = style.reshape(batch, in_channel)
         fwd, bwd, wsq = self._derived()
         if not self.demodulate:
             wsq = None  # demod[b,o] = rsqrt(s^2 @ wsq^T + eps) is computed inside the kernels (model.py:241-243)
         if self.downsample:
-            if torch.is_grad_enabled() and (input.requires_grad or style.requires_grad):
+            if torch.is_grad_enabled() and (input.requires_grad or style.requires_grad or train):
                 raise NotImplementedError("down-sampling ModulatedConv2d (no caller in the generator) is forward-only")
             x = self.blur(input)
             d = K.demod_coefficients(s2d.contiguous(), wsq) if wsq is not None else None
@@ -270,7 +304,8 @@ class ModulatedConv2d(nn.Module):
         else:
             if self.upsample and (self.kernel_size != 3 or tuple(self.blur.kernel.shape) != (4, 4)):
                 raise NotImplementedError("up-sampling ModulatedConv2d: kernel_size 3 with a 4-tap blur")
-            out = K.modconv(input, s2d, wsq, (fwd, bwd), self.blur.kernel if self.upsample else None, self.upsample)
+            out = K.modconv(input, s2d, wsq, (fwd, bwd), self.blur.kernel if self.upsample else None, self.upsample,
+                            weight=self.weight if train else None, wscale=self.scale)
         return out, style
 
 
@@ -314,7 +349,7 @@ class StyledConv(nn.Module):
         conv = self.conv
         batch = input.shape[0]
         fusable = (conv.kernel_size == 3 and not conv.downsample and noise is not None and noise.ndim == 4
-                   and noise.shape[0] == 1 and noise.shape[1] == 1 and not _trainable_weight(conv)
+                   and noise.shape[0] == 1 and noise.shape[1] == 1
                    and not (conv.upsample and tuple(conv.blur.kernel.shape) != (4, 4)))
         self._act_noise = None  # (set below when the fused epilogue produced the output: what a following ToRGB may fold, see _synthesis)
         if not fusable:
@@ -323,13 +358,14 @@ class StyledConv(nn.Module):
             out = self.noise(out, noise=noise)
             return self.activate(out), style
         style = conv._style(style, batch, input_is_stylespace)
+        train = _trainable_weight(conv)
         s2d = style.reshape(batch, conv.in_channel)
         fwd, bwd, wsq = conv._derived()
         noise_c = noise.contiguous()
         link = K.ActLink(noise_c) if (torch.is_grad_enabled() and not conv.upsample) else None
         out = K.styled_conv(input, s2d, wsq if conv.demodulate else None, noise_c, self.noise.weight, self.activate.bias, (fwd, bwd),
                             conv.blur.kernel if conv.upsample else None, conv.upsample, link=link,
-                            demod=demod if conv.demodulate else None)
+                            demod=demod if conv.demodulate else None, weight=conv.weight if train else None, wscale=conv.scale)
         self._act_noise = link
         return out, style
 
@@ -536,7 +572,9 @@ class Generator(nn.Module):
             input_is_stylespace = True
         demods = {}
         if batched is not None and batched[0].is_cuda:  # every layer's style is known: all demodulation vectors in one launch
-            idx = [n for n, (m, is_rgb, _, _) in enumerate(plan) if not is_rgb and m.conv.demodulate and m.conv.kernel_size == 3]
+            # (trained layers are left out: their StyledConv derives wsq and d from the live weight itself)
+            idx = [n for n, (m, is_rgb, _, _) in enumerate(plan)
+                   if not is_rgb and m.conv.demodulate and m.conv.kernel_size == 3 and not m.conv._live()]
             if idx:
                 demods = dict(zip(idx, K.demod_coefficients_all([batched[n] for n in idx], [plan[n][0].conv._derived()[2] for n in idx])))
         producer = None  # the fused-epilogue record of the StyledConv whose output `out` currently is
