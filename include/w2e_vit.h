@@ -95,6 +95,24 @@ int w2e_gemm_pk_h(const float* a_packed, const void* b_packed_half, float* c, in
                   int splits, void* stream);
 int w2e_gemm_pk_h_splits(int m, int n, int k);
 
+/* ---- the CLIP text tower (csrc/text.hip) on the block kernels above: embed -> per block reduce+LN, QKV GEMM, causal attention,
+ * out-proj GEMM, reduce+LN, c_fc GEMM, reduce + QuickGELU, c_proj GEMM -> pool.  Forward only (integer tokens, frozen CLIP).
+ * x[b*seq + l] = token_embedding[tokens[b, l]] + positional[l]  (out [B*seq, dim] row-major; token_embedding [vocab, dim]).  tokens
+ * [B, seq] are int32 (token_bytes 4) or int64 (8), read in place; an id outside [0, vocab) is checked before any load and its row
+ * written as NaN.  1 <= seq <= 96, dim in {512, 768, 1024}. */
+int w2e_text_embed(const void* tokens, int token_bytes, const float* token_embedding, int64_t vocab, const float* positional, float* out,
+                   int batch, int seq, int dim, void* stream);
+/* The causal twin of w2e_attn2_fwd, same operands: out = softmax(Q K^T / 8 + triu(-inf, 1)) V per (batch, head) with qkv the sum of
+ * nsplit slabs [B*seq, 3*heads*64] (+ bias), added in ascending order.  1 <= seq <= 96, heads*64 in {512, 768, 1024}; rows >= seq of
+ * a sequence do not exist and nothing is written for them (nor for the padded rows of a packed output). */
+int w2e_attn_causal_fwd(const float* qkv, int nsplit, int64_t slab, const float* bias, float* out, int batch, int seq, int heads,
+                        int out_packed_rows, void* stream);   /* out_packed_rows > 0: out written K-quad-major (w2e_gemm_pk's A operand) */
+/* EOT pooling: per sequence the first index of its largest token (torch.argmax), and for that row only x = sum of the nsplit slabs
+ * [B*seq, dim] (+ bias[dim]) (+ residual [B*seq, dim]), out[b] = LayerNorm(x) * gamma + beta  (out [B, dim]; ln_final).  The text
+ * projection that follows is a plain GEMM. */
+int w2e_text_pool(const float* part, int nsplit, int64_t slab, const float* bias, const float* residual, const void* tokens,
+                  int token_bytes, int batch, int seq, const float* gamma, const float* beta, float eps, float* out, int dim, void* stream);
+
 /* ---- the scalar tail of a mapper step (csrc/losstail.hip): ~37 [B,T]- / [B,18,512]-sized stock launches as four -------------------
  * criteria/clip_loss.py:16 + the tail of OpenAI clip.model.CLIP.forward: out[b,t] = exp(*logit_scale) * <f_b, t_t> / (|f_b| |t_t|)
  * (feat [B,D], text [T,D], logit_scale a DEVICE scalar holding the log of the scale); similarity != 0: out = 1 - that / 100 (the

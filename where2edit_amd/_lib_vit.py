@@ -22,6 +22,9 @@ PROTOS = {
     "w2e_pack_kq_h": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "w2e_gemm_pk_h": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "w2e_gemm_pk_h_splits": (_I, [_I, _I, _I]),
+    "w2e_text_embed": (_I, [_P, _I, _P, _L, _P, _P, _I, _I, _I, _P]),
+    "w2e_attn_causal_fwd": (_I, [_P, _I, _L, _P, _P, _I, _I, _I, _I, _P]),
+    "w2e_text_pool": (_I, [_P, _I, _L, _P, _P, _P, _I, _I, _I, _P, _P, _F, _P, _I, _P]),
     "w2e_clip_logits_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "w2e_clip_logits_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "w2e_step_loss_fwd": (_I, [_P, _I, _P, _P, _L, _F, _F, _P, _P]),

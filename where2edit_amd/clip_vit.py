@@ -6,8 +6,9 @@ published `clip/model.py` (VisionTransformer, ResidualAttentionBlock, QuickGELU,
 
 fp32 throughout.  The visual tower runs its LayerNorm / QKV / attention / projection / MLP on the hand-written
 kernels of libw2e.so (include/w2e_vit.h, vit_hip.vision_forward) and has no other execution: a CPU tensor raises.
-The text tower (`Transformer` below, stock PyTorch-ROCm ops) runs once on constant tokens and is cached (coach.py:55
-tokenises the description once).  A stock-op composition of the visual tower for A/B timing lives in tools/vit_stock.py.
+The text tower runs on the same block kernels with a causal attention kernel (csrc/text.hip, vit_hip.text_forward) when its
+tokens are on the GPU and no text parameter needs a gradient; otherwise on the stock composition (`Transformer` below).  The mapper
+step tokenises its description once and caches the features (encode_text_cached).  A stock-op composition of the visual tower for A/B timing lives in tools/vit_stock.py.
 """
 import math
 from collections import OrderedDict
@@ -138,7 +139,8 @@ class CLIP(nn.Module):
         return self.visual.conv1.weight.dtype
 
     def set_precision(self, precision):
-        """The image tower's GEMM operand precision: see VisionTransformer.set_precision (parameters and I/O stay fp32)."""
+        """The image tower's GEMM operand precision: see VisionTransformer.set_precision (parameters and I/O stay fp32).  The text
+        tower is not affected: it always runs in fp32."""
         self.visual.set_precision(precision)
         return self
 
@@ -146,6 +148,15 @@ class CLIP(nn.Module):
         return self.visual(image.to(self.dtype))
 
     def encode_text(self, text):
+        """Integer tokens [B, ctx] -> text features [B, embed_dim].  On the GPU with a 512 / 768 / 1024-wide tower, ctx <= 96 and no text
+        parameter that needs a gradient, the tower runs on the HIP kernels (vit_hip.text_forward); otherwise, or with W2E_TEXT_STOCK=1,
+        on the stock composition `_encode_text_stock`."""
+        from . import vit_hip
+        if vit_hip.text_hip_ok(self, text):
+            return vit_hip.text_forward(self, text)
+        return self._encode_text_stock(text)
+
+    def _encode_text_stock(self, text):
         x = self.token_embedding(text) + self.positional_embedding[: text.shape[1]]
         x = self.ln_final(self.transformer(x))
         return x[torch.arange(x.shape[0], device=x.device), text.argmax(dim=-1)] @ self.text_projection

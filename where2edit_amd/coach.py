@@ -386,10 +386,15 @@ def memset_guard(body, what):
         body()
         torch.cuda.synchronize()
     events = prof.events()
-    if not any(e.kernels for e in events):
+    # device-side events: those attached to a torch op (e.kernels) and those of launches no torch op made (the library's own entry
+    # points called through ctypes: a body made only of them, such as CLIP.encode_text's HIP tower, has no op to attach them to)
+    device = [e for e in events if e.device_type == torch.autograd.DeviceType.CUDA]
+    if not any(e.kernels for e in events) and not device:
         raise RuntimeError(f"{what} could not be checked for memset operations: the profiler delivered no device-side events "
                            "(another profiler attached?) -- refusing to capture it; run eagerly (bench.py --graph off)")
-    memsets = sorted({e.name for e in events if any("emset" in k.name or "fillBuffer" in k.name for k in (e.kernels or []))})
+    is_memset = lambda name: "emset" in name or "fillBuffer" in name  # noqa: E731
+    memsets = sorted({e.name for e in events if any(is_memset(k.name) for k in (e.kernels or []))} |
+                     {e.name for e in device if is_memset(e.name)})
     if memsets:
         raise RuntimeError(f"{what} issues memset operations (from {', '.join(memsets)}); they are not replayed "
                            "reliably inside a hipGraph here -- use an elementwise / kernel-based form (tools/graph_safety.py lists them)")

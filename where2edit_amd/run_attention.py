@@ -370,7 +370,8 @@ class RegionAttentionTrainer:
     `perceptual_loss.PerceptualLoss` -- the reference's own identity term (:1007, :1277, :1288: loss_identity = the VGG16
     relu2_2 perceptual loss of img_gen against rank 0's first sample) -- or `identity_loss`, a module `(img_gen, img_orig) ->
     (loss, _)` such as IDLoss; at most one of the two; with neither the term is off.  Text prompts: the reference samples
-    phrases and tokenises them with OpenAI's BPE (not in this image); callers pass CLIP text features / token ids."""
+    phrases and tokenises them with OpenAI's BPE (not in this image); callers pass either the token ids [B, ctx] (integer: the
+    trainer encodes them with the CLIP model's encode_text, :1137-1139) or precomputed CLIP text features [B, embed_dim] (float)."""
 
     def __init__(self, g_ema, clip_loss, mapper, *, attention_layer=13, lr=0.01, steps=10000, lambda_ess=0.03, lambda_sec=0.01,
                  lambda_id=0.1, lambda_delta=0.03, identity_loss=None, consistency="recompute", device="cuda:0", amp=False,
@@ -450,14 +451,18 @@ class RegionAttentionTrainer:
 
     def losses(self, w1, w2, attention_text_features):
         """Everything up to `loss_total` for this rank's latents w1, w2 [B,18,512] (the two fresh batches of :1090 and
-        :1189) and the attention prompt's CLIP text features [B,512] (:1139).  Returns (loss_total, dict, img_gen)."""
+        :1189) and the attention prompt: its CLIP text features [B,512] (:1139), or its integer token ids [B, ctx], of which only
+        row 0 is encoded (the loop uses text_features_attention[[0]], :1141).  Returns (loss_total, dict, img_gen)."""
         import torch.distributed as dist
         batch = w1.shape[0]
         t = self.global_step / self.steps
         img_orig, _, _ = self._generate(w1)
         with torch.no_grad():
             clip_features_origin = self._encode_image(img_orig)  # :1163-1172 (clip_features_origin = image_features_origin)
-            first_text = attention_text_features[:1].float().clone()
+            if attention_text_features.is_floating_point():
+                first_text = attention_text_features[:1].float().clone()
+            else:  # token ids: the reference's text_attention (:1137-1139), encoded here
+                first_text = self.clip_loss.model.encode_text(attention_text_features[:1]).float().clone()
             if self.world > 1:
                 dist.broadcast(first_text, 0)
             first_text = first_text.repeat(batch, 1)

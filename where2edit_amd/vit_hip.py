@@ -4,6 +4,7 @@ and `vision_forward`, the HIP execution of clip_vit.VisionTransformer.forward.
 
 CLIP is a frozen critic here (criteria/clip_loss.py builds it once and never optimises it), so the
 Functions return input gradients only; asking for a weight gradient raises."""
+import ctypes
 import os
 
 import torch
@@ -427,6 +428,72 @@ def vision_forward(vit, image):
             x = resblock_forward(blk, x, vit.heads, arena)
     x = layer_norm(x[:, 0, :], vit.ln_post)
     return linear(x, vit.proj.t())  # [B,768] x [768,512]
+
+
+# ---------------------------------------------------------------------------------------------- the text tower (csrc/text.hip)
+def _text_params(clip):
+    return [clip.token_embedding.weight, clip.positional_embedding, clip.ln_final.weight, clip.ln_final.bias, clip.text_projection,
+            *clip.transformer.parameters()]
+
+
+def text_hip_ok(clip, tokens):
+    """CLIP.encode_text's dispatch rule: the HIP tower takes integer tokens [B, L <= 96] on the GPU the text weights live on, a width the
+    block kernels are instantiated for (512 / 768 / 1024 = heads * 64), no text parameter that would need a gradient, and no
+    W2E_TEXT_STOCK.  Anything else runs the stock composition unchanged."""
+    width = clip.transformer.width
+    heads = clip.transformer.resblocks[0].attn.n_head if len(clip.transformer.resblocks) else 0
+    w = clip.token_embedding.weight
+    if os.environ.get("W2E_TEXT_STOCK") or not tokens.is_cuda or not w.is_cuda or tokens.device != w.device:
+        return False
+    if tokens.ndim != 2 or tokens.dtype not in (torch.int32, torch.int64) or not 1 <= tokens.shape[1] <= min(96, clip.positional_embedding.shape[0]):
+        return False
+    if width not in (512, 768, 1024) or width != heads * 64 or w.dtype != torch.float32:
+        return False
+    return not (torch.is_grad_enabled() and any(p.requires_grad for p in _text_params(clip)))
+
+
+def text_forward(clip, tokens):
+    """CLIP.encode_text on the block kernels: embed -> per block the visual tower's forward (_TransformerV3) with the causal attention
+    kernel in place of attn2 -> EOT pooling + ln_final -> text_projection.  Forward only (no autograd node: the input is integer tokens
+    and the tower is frozen); the packed weights are cached per parameter version in clip._text_wpk."""
+    b, l = tokens.shape
+    dim = clip.transformer.width
+    heads = clip.transformer.resblocks[0].attn.n_head
+    dev = tokens.device
+    tok = _c(tokens)
+    tbytes = tok.element_size()
+    emb = clip.token_embedding.weight
+    if b == 0:
+        return torch.empty((0, clip.text_projection.shape[1]), device=dev, dtype=torch.float32)
+    if not hasattr(clip, "_text_wpk"):
+        clip._text_wpk = _WeightsPk(False)
+    wpk = clip._text_wpk
+    m = b * l
+    mpad = _pad(m, 32)
+    with torch.no_grad():
+        x = torch.empty((m, dim), device=dev, dtype=torch.float32)
+        call("w2e_text_embed", ctypes.c_void_p(tok.data_ptr()), tbytes, ptr(_c(emb.detach())), emb.shape[0],
+             ptr(_c(clip.positional_embedding.detach())), ptr(x), b, l, dim, stream_ptr())
+        pend, pbias, pres = x.view(1, m, dim), None, None
+        for blk in clip.transformer.resblocks:
+            ln1_w, ln1_b, in_w, in_b, out_w, out_b, ln2_w, ln2_b, fc_w, fc_b, proj_w, proj_b = (t.detach() for t in _block_params(blk))
+            xr, y1, _, _ = _reduce_ln(pend, pbias, pres, ln1_w, ln1_b, blk.ln_1.eps, mpad=mpad)
+            qkv = _gemm_pk(y1, m, mpad, wpk.fwd(blk.attn.in_proj_weight))
+            att = torch.empty((dim // 4, mpad, 4), device=dev, dtype=torch.float32)
+            call("w2e_attn_causal_fwd", ptr(qkv), qkv.shape[0], m * 3 * dim, ptr(in_b), ptr(att), b, l, heads, mpad, stream_ptr())
+            o = _gemm_pk(att, m, mpad, wpk.fwd(blk.attn.out_proj.weight))
+            x_mid, y2, _, _ = _reduce_ln(o, out_b, xr, ln2_w, ln2_b, blk.ln_2.eps, mpad=mpad)
+            hp = _gemm_pk(y2, m, mpad, wpk.fwd(blk.mlp.c_fc.weight))
+            n_fc = fc_w.shape[0]
+            h = torch.empty((m, n_fc), device=dev, dtype=torch.float32)
+            g = torch.empty((n_fc // 4, mpad, 4), device=dev, dtype=torch.float32)
+            call("w2e_reduce_gelu", ptr(hp), hp.shape[0], m * n_fc, ptr(fc_b), None, ptr(h), ptr(g), m, n_fc, 0, mpad, stream_ptr())
+            pend = _gemm_pk(g, m, mpad, wpk.fwd(blk.mlp.c_proj.weight))
+            pbias, pres = proj_b, x_mid
+        pooled = torch.empty((b, dim), device=dev, dtype=torch.float32)
+        call("w2e_text_pool", ptr(pend), pend.shape[0], m * dim, ptr(pbias), ptr(pres), ctypes.c_void_p(tok.data_ptr()), tbytes, b, l,
+             ptr(clip.ln_final.weight.detach()), ptr(clip.ln_final.bias.detach()), float(clip.ln_final.eps), ptr(pooled), dim, stream_ptr())
+        return _gemm(pooled, _c(clip.text_projection.detach()), False)
 
 
 # ---------------------------------------------------------------------------------------------- the scalar tail of a step
