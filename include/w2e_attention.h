@@ -9,8 +9,13 @@
  *   w2e_cluster_pool      :843-884  per-(sample, cluster) mean (the reference's Python loop over B*K boolean masks),
  *                                   straight-through threshold 0.8, torchvision gaussian_blur(5)
  * Same conventions as w2e.h (device fp32 pointers, caller-allocated outputs / workspaces, stream as void*, 0 = OK).
- * Forward only: the reference's schedule keeps every `attention*` / `initial*` parameter frozen for the whole run
- * (run_attention.py:1076-1083, `t < 1.15` is always true), so no gradient ever flows through these kernels.
+ * The reference's schedule keeps every `attention*` / `initial*` parameter frozen while `t < 1.15` (run_attention.py:1076-1083),
+ * which always holds, so by default only the forward kernels run.  A user who lowers that literal trains the branch: the
+ * opt-in backward is
+ *   w2e_attention_logits_train   the forward above, also keeping the 32 conv sums per (source, pixel) for the backward
+ *   w2e_attention_logits_bwd     g_each -> every mask parameter's gradient (no gradient for the cached activations)
+ *   w2e_cluster_pool_bwd         g_final + the gradients of loss_reg / loss_tv -> g_each
+ * All fp32, no atomics, no memsets, fixed-order reductions (bit-reproducible), no host synchronisation.
  */
 #ifndef W2E_ATTENTION_H
 #define W2E_ATTENTION_H
@@ -72,6 +77,50 @@ int w2e_attention_logits(const w2e_att_source* sources, int n_sources, const flo
  * final = 5x5 gaussian (sigma 1.1, reflect padding) of thr.  size <= 128, K <= 32.  thr may be NULL. */
 int w2e_cluster_pool(const float* each, const int32_t* assign, float* same, float* means, float* counts, float* thr,
                      float* final_map, int batch, int size, int csize, int clusters, float threshold, void* stream);
+
+/* w2e_attention_logits with one more output: pre[j,b,o,p] = sum_i wscaled_j[i,o] * style_j[b,i] * feat_j[b,i,src(p)], the
+ * modulated conv sums before demodulation ([n_sources, B, 32, size*size]); w2e_attention_logits_bwd reads them instead of
+ * walking the activations a second time.  `partial` is an output here too (the backward reads it).  Same `each`, bit for bit. */
+int w2e_attention_logits_train(const w2e_att_source* sources, int n_sources, const float* wlast, const float* s_last,
+                               const float* d_last, const float* bias_last, const float* noise_last, const float* nw_last,
+                               const float* initial_bias, float* partial, float* each, float* pre, int batch, int size,
+                               void* stream);
+
+/* Gradients of one source (all written, not accumulated; the paths through demod_j are included). */
+typedef struct {
+    float* g_wscaled;  /* [channels, 32] */
+    float* g_style;    /* [B, channels] */
+    float* g_bias;     /* [32] */
+    float* g_noise_w;  /* [1] (0 when the source's noise is NULL) */
+} w2e_att_source_grad;
+
+/* Floats of workspace w2e_attention_logits_bwd needs (sum_channels = sum of the sources' channel counts):
+ *   B*P + 4*B + n*B*32*P + n*B*ceil(P/256)*97 + n*B*32 + B*sum_channels*32      with P = size*size, n = n_sources */
+#define W2E_ATT_BWD_WORKSPACE(n, B, P, sum_channels)                                                                   \
+    ((int64_t)(B) * (P) + 4 * (int64_t)(B) + (int64_t)(n) * (B) * 32 * (P) + (int64_t)(n) * (B) * (((P) + 255) / 256) * 97 + \
+     (int64_t)(n) * (B) * 32 + (int64_t)(B) * (sum_channels) * 32)
+
+/* Backward of w2e_attention_logits_train.  g_each, each [B,size*size]; sources / wlast / s_last / d_last / biases / noises
+ * exactly as the forward got them; partial and pre as the forward wrote them.  Outputs (written): grads[j] per source,
+ * g_wlast [32n], g_s_last [B,32n] (both include the path through d_last, eps-free: d d_last / d x = -d_last^3 * x * w^2),
+ * g_scalars [3] = gradients of initial_bias, bias_last, nw_last (the last is 0 when noise_last is NULL).
+ * workspace: W2E_ATT_BWD_WORKSPACE floats (workspace_floats is checked against it).  Deterministic, no atomics. */
+int w2e_attention_logits_bwd(const w2e_att_source* sources, const w2e_att_source_grad* grads, int n_sources, const float* wlast,
+                             const float* s_last, const float* d_last, const float* bias_last, const float* noise_last,
+                             const float* nw_last, const float* partial, const float* pre, const float* each,
+                             const float* g_each, float* g_wlast, float* g_s_last, float* g_scalars, float* workspace,
+                             int64_t workspace_floats, int batch, int size, void* stream);
+
+/* Adjoint of w2e_cluster_pool plus the two loss terms of the net (run_attention.py:851-871):
+ *   g_thr  = adjoint of the reflect-padded 5x5 gaussian applied to g_final (border taps fold back)
+ *   g_same = g_thr (the straight-through threshold has slope 1 on both sides); 0 where the cluster id is out of range
+ *   g_mean[b,k] = sum_{p in k} g_same[p] + g_loss_reg/B * [count > 0 and mean > 0.7]
+ *   g_each[p] = g_mean[b,k(p)] / count[b,k(p)] + g_loss_tv * 2 (each[p] - same[p]) / (B*size*size)
+ * g_loss_reg / g_loss_tv: device scalars (the upstream gradients of loss_reg = sum relu(mean - 0.7) / B and
+ * loss_tv = mse(each, same.detach())), or NULL for 0.  g_final may be NULL for 0.  size <= 128, K <= 32. */
+int w2e_cluster_pool_bwd(const float* g_final, const float* each, const float* same, const float* means, const float* counts,
+                         const int32_t* assign, const float* g_loss_reg, const float* g_loss_tv, float* g_each, int batch,
+                         int size, int csize, int clusters, void* stream);
 
 #ifdef __cplusplus
 }

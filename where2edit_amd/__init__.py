@@ -34,3 +34,11 @@ def train_conv_weights(module):
     its gradient from the conv-weight-gradient kernels; stylegan2.freeze_conv_weights undoes it."""
     from .stylegan2 import train_conv_weights as _train
     return _train(module)
+
+
+def train_mask_branch(net, enabled=True):
+    """Opt-in training of the region-attention mask branch (run_attention.train_mask_branch): every `attention*` / `initial*`
+    parameter of `net` requires grad and gets its gradient from the mask-branch backward kernels; run_attention.freeze_mask_branch
+    (or enabled=False) undoes it."""
+    from .run_attention import train_mask_branch as _train
+    return _train(net, enabled)

@@ -166,6 +166,7 @@ struct AttLaunch {
     const float* wlast;
     const float* s_last;
     float* partial;
+    float* pre;  // [n_sources][B][32][size*size] modulated conv sums before demodulation, or NULL (saved for w2e_attention_logits_bwd)
     int n_sources, batch, size;
 };
 
@@ -174,6 +175,9 @@ constexpr int ATT_CH = 128;  // channels staged per LDS pass: [128][32] floats =
 // grid (pixel tiles of 256, batch, source).  A thread owns one output pixel and the 32 outputs of its source's 1x1 conv;
 // the modulated weights scale*W[o,i]*s[b,i] of a 128-channel slice sit in LDS as [i][32] (8 broadcast ds_read_b128 per
 // channel for 32 FMAs).  Writes the source's contribution to the final 576->1 conv: sum_o wlast*s_last*a[o].
+// SAVE: also keep the 32 conv sums of every pixel for the backward (the opt-in trainable mask branch); the default
+// instantiation is the forward-only kernel, unchanged.
+template <bool SAVE>
 __global__ __launch_bounds__(256) void att_source_kernel(const AttLaunch L) {
     __shared__ __attribute__((aligned(16))) float wm[ATT_CH * 32];
     __shared__ float dcoef[32], bcoef[32], lcoef[32];
@@ -217,6 +221,11 @@ __global__ __launch_bounds__(256) void att_source_kernel(const AttLaunch L) {
     if (!live) return;
     const float nz = s.noise ? s.noise_w[0] * s.noise[(int64_t)b * size * size + pix] : 0.f;
     float z = 0.f;
+    if (SAVE) {
+        float* pre = L.pre + ((int64_t)j * L.batch + b) * 32 * size * size + pix;
+#pragma unroll
+        for (int o = 0; o < 32; ++o) pre[(int64_t)o * size * size] = acc[o];
+    }
 #pragma unroll
     for (int o = 0; o < 32; ++o) {
         float v = acc[o] * dcoef[o] + nz + bcoef[o];
@@ -366,11 +375,12 @@ extern "C" int w2e_attention_demod(const w2e_att_source* sources, int n_sources,
     return 0;
 }
 
-extern "C" int w2e_attention_logits(const w2e_att_source* sources, int n_sources, const float* wlast, const float* s_last,
-                                    const float* d_last, const float* bias_last, const float* noise_last,
-                                    const float* nw_last, const float* initial_bias, float* partial, float* each, int batch,
-                                    int size, void* stream) {
+static int attention_logits_launch(const w2e_att_source* sources, int n_sources, const float* wlast, const float* s_last,
+                                   const float* d_last, const float* bias_last, const float* noise_last, const float* nw_last,
+                                   const float* initial_bias, float* partial, float* each, float* pre, bool save, int batch,
+                                   int size, void* stream) {
     W2E_REQUIRE(sources && wlast && s_last && d_last && bias_last && initial_bias && partial && each, "attention_logits: null tensor");
+    W2E_REQUIRE(!save || pre, "attention_logits_train: null pre");
     W2E_REQUIRE(n_sources >= 1 && n_sources <= W2E_ATT_MAX_SOURCES, "attention_logits: 1 <= n_sources <= %d", W2E_ATT_MAX_SOURCES);
     W2E_REQUIRE(batch >= 0 && size > 0, "attention_logits: bad dims");
     W2E_REQUIRE(!noise_last || nw_last, "attention_logits: noise_last without nw_last");
@@ -383,16 +393,33 @@ extern "C" int w2e_attention_logits(const w2e_att_source* sources, int n_sources
         W2E_REQUIRE(!s.noise || s.noise_w, "attention_logits: source %d: noise without noise_w", j);
         L.src[j] = s;
     }
-    L.wlast = wlast, L.s_last = s_last, L.partial = partial, L.n_sources = n_sources, L.batch = batch, L.size = size;
+    L.wlast = wlast, L.s_last = s_last, L.partial = partial, L.pre = pre, L.n_sources = n_sources, L.batch = batch, L.size = size;
     hipStream_t s = (hipStream_t)stream;
     const int npix = size * size;
     dim3 grid((unsigned)ceil_div(npix, 256), (unsigned)batch, (unsigned)n_sources);
-    att_source_kernel<<<grid, 256, 0, s>>>(L);
+    if (save) att_source_kernel<true><<<grid, 256, 0, s>>>(L);
+    else att_source_kernel<false><<<grid, 256, 0, s>>>(L);
     W2E_LAUNCH_CHECK("attention_logits (sources)");
     att_finish_kernel<<<(unsigned)ceil_div((int64_t)batch * npix, 256), 256, 0, s>>>(partial, d_last, bias_last, noise_last, nw_last,
                                                                                     initial_bias, each, n_sources, batch, npix);
     W2E_LAUNCH_CHECK("attention_logits (finish)");
     return 0;
+}
+
+extern "C" int w2e_attention_logits(const w2e_att_source* sources, int n_sources, const float* wlast, const float* s_last,
+                                    const float* d_last, const float* bias_last, const float* noise_last,
+                                    const float* nw_last, const float* initial_bias, float* partial, float* each, int batch,
+                                    int size, void* stream) {
+    return attention_logits_launch(sources, n_sources, wlast, s_last, d_last, bias_last, noise_last, nw_last, initial_bias, partial,
+                                   each, nullptr, false, batch, size, stream);
+}
+
+extern "C" int w2e_attention_logits_train(const w2e_att_source* sources, int n_sources, const float* wlast, const float* s_last,
+                                          const float* d_last, const float* bias_last, const float* noise_last,
+                                          const float* nw_last, const float* initial_bias, float* partial, float* each,
+                                          float* pre, int batch, int size, void* stream) {
+    return attention_logits_launch(sources, n_sources, wlast, s_last, d_last, bias_last, noise_last, nw_last, initial_bias, partial,
+                                   each, pre, true, batch, size, stream);
 }
 
 extern "C" int w2e_cluster_pool(const float* each, const int32_t* assign, float* same, float* means, float* counts,

@@ -16,10 +16,13 @@ loss_tv])`.  What is different by design (MI355X-first):
   * the Python loop over B*K boolean masks (:855-868) is a per-sample reduction kernel that also applies the
     threshold and the 5x5 gaussian (`w2e_cluster_pool`).
 
-The mask branch is forward-only: the reference keeps every `attention*` / `initial*` parameter frozen for the whole run
-(:1076-1083, `t < 1.15` always holds), so nothing ever differentiates through it; if one of those parameters requires
-grad while gradients are enabled this module raises instead of silently returning a constant mask.  The style branch
-(`mapper_*`) is [B,1,C]-sized GEMMs on rocBLAS through torch + the fused bias/LeakyReLU op, fully differentiable."""
+By default the mask branch is forward-only: the reference keeps every `attention*` / `initial*` parameter frozen while
+`t < 1.15` (:1076-1083), which always holds; if one of those parameters requires grad while gradients are enabled this
+module raises instead of silently returning a constant mask.  `train_mask_branch(net)` opts in to the differentiable
+branch (the same forward kernels inside autograd Functions whose backward is `w2e_cluster_pool_bwd` +
+`w2e_attention_logits_bwd`), and `RegionAttentionTrainer(train_mask_from=T)` is the reference's literal as a parameter.
+The style branch (`mapper_*`) is [B,1,C]-sized GEMMs on rocBLAS through torch + the fused bias/LeakyReLU op, fully
+differentiable."""
 import ctypes
 
 import torch
@@ -31,6 +34,10 @@ from ._lib import call, ptr, stream_ptr
 from .stylegan2 import EqualLinear, StyledConv
 
 _I32P = ctypes.c_void_p
+
+
+class _AttSourceGrad(ctypes.Structure):  # w2e_att_source_grad (include/w2e_attention.h)
+    _fields_ = [("g_wscaled", ctypes.c_void_p), ("g_style", ctypes.c_void_p), ("g_bias", ctypes.c_void_p), ("g_noise_w", ctypes.c_void_p)]
 
 
 class _AttSource(ctypes.Structure):  # w2e_att_source (include/w2e_attention.h)
@@ -47,6 +54,11 @@ PROTOS = {
                              [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "w2e_attention_demod": (ctypes.c_int, [ctypes.POINTER(_AttSource), ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_void_p]),
     "w2e_cluster_pool": (ctypes.c_int, [ctypes.c_void_p] * 7 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_void_p]),
+    "w2e_attention_logits_train": (ctypes.c_int, [ctypes.POINTER(_AttSource), ctypes.c_int] + [ctypes.c_void_p] * 10 +
+                                   [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "w2e_attention_logits_bwd": (ctypes.c_int, [ctypes.POINTER(_AttSource), ctypes.POINTER(_AttSourceGrad), ctypes.c_int] +
+                                 [ctypes.c_void_p] * 14 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "w2e_cluster_pool_bwd": (ctypes.c_int, [ctypes.c_void_p] * 9 + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
 }
 
 
@@ -120,6 +132,131 @@ def cluster_pool(each, assign, size, clusters, threshold=0.8):
     return same, means, counts, thr, final
 
 
+def _pool_losses(each, same, means, counts):
+    """:851-869: sum over non-empty clusters of relu(mean - 0.7), averaged over the batch; :871 MSE(each, same)."""
+    loss_reg = (torch.relu(means - 0.7) * (counts > 0)).sum().reshape(1) / float(each.shape[0])
+    return loss_reg, F.mse_loss(each, same)
+
+
+class _ClusterPoolTrain(torch.autograd.Function):
+    """cluster_pool + the two loss terms with a backward (w2e_cluster_pool_bwd): (final, loss_reg, loss_tv) carry gradients to
+    `each`; same / means / counts / thresholded are returned for `net.last` and are not differentiable."""
+
+    @staticmethod
+    def forward(ctx, each, assign, size, clusters):
+        each = each.contiguous()
+        same, means, counts, thr, final = cluster_pool(each, assign, size, clusters)
+        loss_reg, loss_tv = _pool_losses(each, same, means, counts)
+        ctx.save_for_backward(each, same, means, counts, assign)
+        ctx.dims = (size, clusters)
+        ctx.mark_non_differentiable(same, means, counts, thr)
+        return final, loss_reg, loss_tv, same, means, counts, thr
+
+    @staticmethod
+    def backward(ctx, g_final, g_reg, g_tv, *_):
+        each, same, means, counts, assign = ctx.saved_tensors
+        size, clusters = ctx.dims
+        g_each = torch.empty_like(each)
+        call("w2e_cluster_pool_bwd", ptr(g_final.contiguous().float()), ptr(each), ptr(same), ptr(means), ptr(counts), _i32ptr(assign),
+             ptr(g_reg.contiguous().float()), ptr(g_tv.contiguous().float()), ptr(g_each), each.shape[0], size, assign.shape[1], clusters,
+             stream_ptr())
+        return g_each, None, None, None
+
+
+def att_bwd_workspace(n, batch, npix, sum_channels):
+    """W2E_ATT_BWD_WORKSPACE (include/w2e_attention.h), in floats."""
+    return (batch * npix + 4 * batch + n * batch * 32 * npix + n * batch * ((npix + 255) // 256) * 97 + n * batch * 32 +
+            batch * sum_channels * 32)
+
+
+class _MaskLogitsTrain(torch.autograd.Function):
+    """each [B,size,size] = w2e_attention_logits over cached activations, differentiable in every parameter-derived input.
+    apply(feats, noises, size, eps, eps_last, wlast, s_last, bias_last, nw_last, initial_bias, *(wscaled_j, style_j, bias_j, nw_j ...)):
+    feats: list of n contiguous [B,C_j,r_j,r_j] activations (no gradient); noises: list of n + 1 [B,size*size] tensors (the last one is
+    attention_last's), the same tensors in forward and backward.  The forward keeps the conv sums (`pre`) for the backward."""
+
+    @staticmethod
+    def _descs(feats, noises, per, demods, batch):
+        n = len(feats)
+        descs = (_AttSource * n)()
+        for j in range(n):
+            wsc, style, bias, nw = per[4 * j:4 * j + 4]
+            d = descs[j]
+            d.feat, d.wscaled, d.style, d.demod, d.bias = (ptr(t).value for t in (feats[j], wsc, style, demods[j], bias))
+            d.noise, d.noise_w = ptr(noises[j]).value, ptr(nw).value
+            d.channels, d.res = feats[j].shape[1], feats[j].shape[2]
+        return descs
+
+    @staticmethod
+    def forward(ctx, feats, noises, size, eps, eps_last, wlast, s_last, bias_last, nw_last, initial_bias, *per):
+        n, batch, dev = len(feats), s_last.shape[0], s_last.device
+        if len(per) != 4 * n or len(noises) != n + 1 or wlast.numel() != 32 * n:
+            raise RuntimeError("mask logits: one (wscaled, style, bias, noise strength) per source and n + 1 noise tensors")
+        per = [t.detach().float().contiguous() for t in per]
+        wlast, s_last, bias_last, nw_last, initial_bias = (t.detach().float().contiguous() for t in (wlast, s_last, bias_last, nw_last, initial_bias))
+        for j in range(n):
+            if per[4 * j].shape != (feats[j].shape[1], 32) or per[4 * j + 1].shape != (batch, feats[j].shape[1]) or \
+                    feats[j].shape[0] != batch or feats[j].shape[2] != feats[j].shape[3] or not feats[j].is_contiguous():
+                raise RuntimeError(f"mask logits: source {j}: feature {tuple(feats[j].shape)}, weight {tuple(per[4 * j].shape)}, "
+                                   f"style {tuple(per[4 * j + 1].shape)}")
+        noises = [t.detach().float().contiguous() for t in noises]
+        if any(t.shape != (batch, size * size) for t in noises):
+            raise RuntimeError("mask logits: every noise tensor is [B, size*size]")
+        demods = torch.empty((n, batch, 32), device=dev, dtype=torch.float32)
+        descs = _MaskLogitsTrain._descs(feats, noises, per, demods, batch)
+        call("w2e_attention_demod", descs, n, batch, float(eps), stream_ptr())
+        d_last = torch.rsqrt((s_last * wlast).square().sum(1) + eps_last).contiguous()
+        partial = torch.empty((n, batch, size * size), device=dev, dtype=torch.float32)
+        pre = torch.empty((n, batch, 32, size * size), device=dev, dtype=torch.float32)
+        each = torch.empty((batch, size, size), device=dev, dtype=torch.float32)
+        call("w2e_attention_logits_train", descs, n, ptr(wlast), ptr(s_last), ptr(d_last), ptr(bias_last), ptr(noises[n]), ptr(nw_last),
+             ptr(initial_bias), ptr(partial), ptr(each), ptr(pre), batch, size, stream_ptr())
+        ctx.save_for_backward(wlast, s_last, bias_last, nw_last, d_last, partial, pre, each, demods, *per)
+        ctx.feats, ctx.noises, ctx.size = feats, noises, size
+        return each
+
+    @staticmethod
+    def backward(ctx, g_each):
+        wlast, s_last, bias_last, nw_last, d_last, partial, pre, each, demods, *per = ctx.saved_tensors
+        feats, noises, size = ctx.feats, ctx.noises, ctx.size
+        n, batch, dev = len(feats), s_last.shape[0], s_last.device
+        descs = _MaskLogitsTrain._descs(feats, noises, per, demods, batch)
+        grads = (_AttSourceGrad * n)()
+        out = []
+        for j in range(n):
+            c = feats[j].shape[1]
+            g = [torch.empty((c, 32), device=dev), torch.empty((batch, c), device=dev), torch.empty(32, device=dev), torch.empty(1, device=dev)]
+            grads[j].g_wscaled, grads[j].g_style, grads[j].g_bias, grads[j].g_noise_w = (ptr(t).value for t in g)
+            out += g
+        g_wlast, g_s_last, g_scalars = torch.empty_like(wlast), torch.empty_like(s_last), torch.empty(3, device=dev)
+        floats = att_bwd_workspace(n, batch, size * size, sum(f.shape[1] for f in feats))
+        work = torch.empty(floats, device=dev, dtype=torch.float32)
+        call("w2e_attention_logits_bwd", descs, grads, n, ptr(wlast), ptr(s_last), ptr(d_last), ptr(bias_last), ptr(noises[n]), ptr(nw_last),
+             ptr(partial), ptr(pre), ptr(each), ptr(g_each.contiguous().float()), ptr(g_wlast), ptr(g_s_last), ptr(g_scalars), ptr(work),
+             floats, batch, size, stream_ptr())
+        return (None, None, None, None, None, g_wlast, g_s_last, g_scalars[1:2], g_scalars[2:3], g_scalars[0:1], *out)
+
+
+def _is_mask_param(name):
+    return name.startswith("attention") or name.startswith("initial")
+
+
+def train_mask_branch(net, enabled=True):
+    """Opt in to (or, with enabled=False, out of) a trainable mask branch: every `attention*` / `initial*` parameter of `net` requires
+    grad and `forward` differentiates through the branch on the HIP backward kernels.  Off by default; without it a mask parameter
+    that requires grad is an error."""
+    net._train_mask = bool(enabled)
+    for n, p in net.named_parameters():
+        if _is_mask_param(n):
+            p.requires_grad_(bool(enabled))
+    return net
+
+
+def freeze_mask_branch(net):
+    """Undo train_mask_branch: the mask branch is forward-only again and its parameters are frozen."""
+    return train_mask_branch(net, False)
+
+
 class FullSpaceMapperFEATClusterLinStyle_Net(nn.Module):
     """run_attention.py:703-752 (constructor) / :754-893 (forward)."""
 
@@ -172,7 +309,7 @@ class FullSpaceMapperFEATClusterLinStyle_Net(nn.Module):
         return hit[1]
 
     def _mask_params_frozen(self):
-        return not any(p.requires_grad for n, p in self.named_parameters() if n.startswith("attention") or n.startswith("initial"))
+        return not any(p.requires_grad for n, p in self.named_parameters() if _is_mask_param(n))
 
     def _wscaled_t(self, conv):
         """(scale * W[0,:,:,0,0])^T as a contiguous [C, 32] tensor, cached per conv until its weight changes."""
@@ -272,6 +409,35 @@ class FullSpaceMapperFEATClusterLinStyle_Net(nn.Module):
         del keep
         return each, assign
 
+    def attention_map_train(self, feature_map, size, attention_text, n_codes, noises=None):
+        """attention_map with gradients (train_mask_branch): the same kernels inside _MaskLogitsTrain.  The style EqualLinears and the
+        [C,32] scaled weights are stock ops on the live parameters (differentiable; no version-keyed cache on this path); the noise of
+        every NoiseInjection is drawn even at strength 0 -- the strength's gradient is sum(g_pre * noise) -- unless `noises` (n + 1
+        tensors [B, size*size], attention_last's last) pins it."""
+        batch, dev = attention_text.shape[0], attention_text.device
+        assign = cluster_assign(feature_map[self.cluster_layer - 1], self.initial_state.to(torch.float32))
+        src = self._sources(n_codes)
+        last = self.attention_last
+        if 32 * len(src) != last.conv.in_channel:
+            raise RuntimeError(f"{len(src)} attention sources for an attention_last of {last.conv.in_channel} channels")
+        eps = src[0][0].conv.eps
+        if any(sc.conv.eps != eps for sc, _, _ in src):
+            raise RuntimeError("the attention sources disagree on the demodulation eps")
+        if noises is None:
+            noises = [torch.randn(batch, size * size, device=dev) for _ in range(len(src) + 1)]
+        feats, per = [], []
+        for j, (sc, aff, fi) in enumerate(src):
+            feat = feature_map[fi].detach()
+            feat = feat if feat.is_contiguous() else feat.contiguous()
+            if feat.shape[1] != sc.conv.in_channel or feat.shape[2] != feat.shape[3]:
+                raise RuntimeError(f"attention source {j}: feature {tuple(feat.shape)} for a {sc.conv.in_channel}-channel conv")
+            feats.append(feat)
+            per += [(sc.conv.weight[0, :, :, 0, 0] * sc.conv.scale).t(), aff(attention_text), sc.activate.bias, sc.noise.weight]
+        wl = last.conv.weight[0, 0, :, 0, 0] * last.conv.scale
+        each = _MaskLogitsTrain.apply(feats, list(noises), size, float(eps), float(last.conv.eps), wl, self.attention_textca_last(attention_text),
+                                      last.activate.bias, last.noise.weight, self.initial_bias, *per)
+        return each, assign
+
     # ---- the style branch (:806-822) ----------------------------------------------------------------------------------
     def new_styles(self, x, x_text, strength_alpha=0.1):
         """`strength_alpha`: the 0.1 of :820; the demo's copy of this net takes it as an argument
@@ -290,20 +456,24 @@ class FullSpaceMapperFEATClusterLinStyle_Net(nn.Module):
                 out.append(x_c.unsqueeze(3).unsqueeze(3))
         return out, loss_delta
 
-    def forward(self, x, feature_map, size, attention_text=None, strength_alpha=0.1):
-        if torch.is_grad_enabled() and not self._mask_params_frozen():
+    def forward(self, x, feature_map, size, attention_text=None, strength_alpha=0.1, _mask_noises=None):
+        trainable = torch.is_grad_enabled() and not self._mask_params_frozen()
+        if trainable and not getattr(self, "_train_mask", False):
             raise RuntimeError("FullSpaceMapperFEATClusterLinStyle_Net: the mask branch (attention*/initial* parameters) is "
                                "forward-only here -- the reference keeps it frozen for the whole run (run_attention.py:1076-1083); "
                                "set requires_grad_(False) on those parameters (RegionAttentionTrainer does)")
         x_text = x[0][:, 0, :self.latent_dim]
         if attention_text is None:
             attention_text = x_text
-        each, assign = self.attention_map(feature_map, size, attention_text.detach().float(), len(x))
-        same, means, counts, thr, final = cluster_pool(each, assign, size, self.clusters)
+        if trainable:  # opted in (train_mask_branch): final, loss_reg and loss_tv carry gradients to the mask parameters
+            each, assign = self.attention_map_train(feature_map, size, attention_text.detach().float(), len(x), _mask_noises)
+            final, loss_reg, loss_tv, same, means, counts, thr = _ClusterPoolTrain.apply(each, assign, size, self.clusters)
+            each = each.detach()
+        else:
+            each, assign = self.attention_map(feature_map, size, attention_text.detach().float(), len(x))
+            same, means, counts, thr, final = cluster_pool(each, assign, size, self.clusters)
+            loss_reg, loss_tv = _pool_losses(each, same, means, counts)
         out, loss_delta = self.new_styles(x, x_text, strength_alpha)
-        # :851-869: sum over non-empty clusters of relu(mean - 0.7), averaged over the batch; :871 MSE(each, same)
-        loss_reg = (torch.relu(means - 0.7) * (counts > 0)).sum().reshape(1) / float(each.shape[0])
-        loss_tv = F.mse_loss(each, same)
         self.last = {"each": each, "same": same, "assign": assign, "pre_blur": thr, "means": means, "counts": counts}
         return out, final, [loss_delta, loss_reg, loss_tv]
 
@@ -375,16 +545,22 @@ class RegionAttentionTrainer:
 
     def __init__(self, g_ema, clip_loss, mapper, *, attention_layer=13, lr=0.01, steps=10000, lambda_ess=0.03, lambda_sec=0.01,
                  lambda_id=0.1, lambda_delta=0.03, identity_loss=None, consistency="recompute", device="cuda:0", amp=False,
-                 perceptual_loss=None):
-        from . import dist as w2e_dist
+                 perceptual_loss=None, train_mask_from=None):
         if identity_loss is not None and perceptual_loss is not None:
             raise ValueError("RegionAttentionTrainer: pass identity_loss or perceptual_loss, not both (both are the lambda_id term)")
+        if train_mask_from is not None:
+            ok = isinstance(train_mask_from, (int, float)) and not isinstance(train_mask_from, bool)
+            if not ok or not train_mask_from >= 0:  # (also refuses NaN)
+                raise ValueError(f"RegionAttentionTrainer: train_mask_from is None (mask branch frozen for the whole run) or a number >= 0, "
+                                 f"the fraction t = step / steps from which the mask branch trains (got {train_mask_from!r})")
+            train_mask_from = float(train_mask_from)
+        self.train_mask_from = train_mask_from
         self.device = device
         self.g_ema = g_ema.to(device).eval().requires_grad_(False)
         self.clip_loss = clip_loss.to(device)
         self.mapper = mapper.to(device)
         for n, p in self.mapper.named_parameters():  # run_attention.py:1076-1083 (t < 1.15 always holds)
-            if n.startswith("attention") or n.startswith("initial"):
+            if _is_mask_param(n):
                 p.requires_grad_(False)
         self.attention_layer = attention_layer
         self.lr, self.steps = lr, steps
@@ -394,7 +570,12 @@ class RegionAttentionTrainer:
         if consistency not in ("recompute", "broadcast"):
             raise ValueError("consistency must be 'recompute' or 'broadcast'")
         self.consistency = consistency
-        self.params = [p for p in self.mapper.parameters() if p.requires_grad]
+        # `train_mask_from` = T is the reference's literal 1.15 (:1076) as a parameter: the optimizer then covers every parameter, as the
+        # reference's does (:1051); a frozen parameter has no gradient and Adam leaves it alone.  None: only the style branch, as before.
+        if train_mask_from is None:
+            self.params = [p for p in self.mapper.parameters() if p.requires_grad]
+        else:
+            self.params = list(self.mapper.parameters())
         self.optimizer = torch.optim.Adam(self.params, lr=lr)
         # `--amp` (run_attention.py:1068-1069, 1231, 1418-1421): the reference wraps the mapper + generator forward in autocast and drives
         # the optimizer through a GradScaler.  The kernels of this package compute in fp32 only, so there is nothing to autocast (a
@@ -407,8 +588,27 @@ class RegionAttentionTrainer:
         import torch.distributed as dist
         self.world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
         self.rank = dist.get_rank() if self.world > 1 else 0
-        self.bucket = w2e_dist.GradBucket(self.params) if self.world > 1 else None
+        self.bucket = None
+        self._mask_on = False
+        self._make_bucket()
         self.global_step = 0
+        self._schedule_mask()
+
+    def _make_bucket(self):
+        from . import dist as w2e_dist
+        self.bucket = w2e_dist.GradBucket(self.params) if self.world > 1 else None  # (covers the parameters that require grad now)
+
+    def _schedule_mask(self):
+        """run_attention.py:1076-1083 with T = train_mask_from in the place of 1.15: the mask branch is frozen while t < T and trains
+        from then on (the all-reduce bucket is rebuilt when that changes, so that it covers the mask parameters too)."""
+        if self.train_mask_from is None:
+            return False
+        on = self.global_step / self.steps >= self.train_mask_from
+        if on != self._mask_on:
+            train_mask_branch(self.mapper, on)
+            self._mask_on = on
+            self._make_bucket()
+        return on
 
     # ---- pieces ------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -498,6 +698,7 @@ class RegionAttentionTrainer:
         self.mapper.train()
         t = self.global_step / self.steps
         self.optimizer.param_groups[0]["lr"] = get_lr(t, self.lr)  # :1072-1074
+        self._schedule_mask()                                       # :1076-1083
         if self.bucket is not None:
             self.bucket.zero()
         else:
