@@ -39,6 +39,29 @@ int w2e_cluster_assign(const float* feat, const float* centroids, int32_t* assig
 int w2e_cluster_accumulate(const float* feat, const int32_t* assign, float* partial, float* counts, int batch, int channels,
                            int pos_channels, int size, int clusters, void* stream);
 
+/* ---- offline k-means at the reference's scale (clustering_feature.py:347-397: 300 x [1,512,128,128] points, sklearn KMeans) ----
+ * One persistent kernel in three modes over the same points ([B,C,S,S] + the 2P analytic position channels), a grid of
+ * `grid` workgroups (w2e_kmeans_plan) walking 128-pixel tiles, each writing one row of `partial` (written, not accumulated):
+ *   mode 0  assignment:  assign[b,y,x] exactly as w2e_cluster_assign (bit-identical distances), mind[b,y,x] = the squared distance
+ *           to that centre (assign / mind may be NULL); partial [grid][1] = the workgroup's share of the inertia.
+ *   mode 1  fused Lloyd step: mode 0 plus the per-cluster sums and counts of the tile, taken while it is still in cache;
+ *           partial [grid][K*(D+1) + 1]: [k][d] sums (d < D = C+2P), [k][D] the count, then the inertia share.  Needs an even S
+ *           and centres + sums within the 160 KB of LDS (w2e_kmeans_plan reports `fused` = 0 otherwise: run mode 0 and
+ *           w2e_cluster_accumulate instead).
+ *   mode 2  k-means++ seeding pass: `centroids` = T <= 8 candidate centres [T][D] (clusters = T); cand_dist[t*cand_ld + n] =
+ *           |x_n - c_t|^2 for every point n = b*S*S + y*S + x (kept so that the chosen candidate is committed with one
+ *           elementwise minimum, no second walk of the features); partial [grid][T] = shares of the T potentials
+ *           sum_n min(mind[n], |x_n - c_t|^2); mind is read (NULL = +inf: the first centre).
+ * No atomics: per-lane running sums in tile order, wave shuffles, one owner per LDS column; the result depends on the data and
+ * on `grid` only.  K <= 32. */
+int w2e_kmeans_plan(int batch, int channels, int pos_channels, int size, int clusters, int* grid, int* fused);
+int w2e_kmeans_pass(int mode, const float* feat, const float* centroids, int32_t* assign, float* mind, float* cand_dist,
+                    int64_t cand_ld, float* partial, int grid, int batch, int channels, int pos_channels, int size, int clusters,
+                    void* stream);
+/* acc[j] += sum over g < rows, in order, of partial[g][j] (j < n), in double: the fixed-order finish of the partials of one pass,
+ * and -- called once per chunk of points -- of the chunks. */
+int w2e_kmeans_reduce(const float* partial, int rows, int n, double* acc, void* stream);
+
 #define W2E_ATT_MAX_SOURCES 32
 /* One source = one cached activation and the 1x1 StyledConv(C, 32, 1, C) applied to it with a style given in S-space:
  *   a[b,o,p] = lrelu( d[b,o] * sum_i wscaled[o,i] * s[b,i] * feat[b,i,src(p)] + nw*noise[b,p] + bias[o] ) * sqrt2

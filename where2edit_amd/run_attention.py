@@ -59,6 +59,11 @@ PROTOS = {
     "w2e_attention_logits_bwd": (ctypes.c_int, [ctypes.POINTER(_AttSource), ctypes.POINTER(_AttSourceGrad), ctypes.c_int] +
                                  [ctypes.c_void_p] * 14 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "w2e_cluster_pool_bwd": (ctypes.c_int, [ctypes.c_void_p] * 9 + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
+    # the offline k-means of clustering_feature.py (csrc/kmeans.hip)
+    "w2e_kmeans_plan": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int)] * 2),
+    "w2e_kmeans_pass": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_int64, ctypes.c_void_p] + [ctypes.c_int] * 6 +
+                        [ctypes.c_void_p]),
+    "w2e_kmeans_reduce": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 
