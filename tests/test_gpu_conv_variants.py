@@ -5,7 +5,8 @@ the register pipeline and an epilogue per launch; w2e_wino_fused picks 4 or 8 ma
 ownership and how many blocks each persistent workgroup walks.  The matrix below (DIRECT_MATRIX; FUSED_SHAPES x FUSED_MW x
 FUSED_LAYOUTS x FUSED_EPIS) is the list of variants these tests run; the census at the end collects the variants real eager steps pick (the library's `tune_print`
 "variant" lines) and fails when one of them is not in the matrix -- a cost-model change that starts to pick an untested
-variant has to add its case here first.
+variant has to add its case here first.  The same census checks the FIR launches of those steps against the matrix of
+tests/test_gpu_fir_variants.py.
 
 Inputs are heavy-tailed (log-normal input-channel scales with x30 outliers, log-normal weight row norms, per-sample in / out
 scales 10x apart), and every result is held both to the global max-norm (assert_close) and to a per-plane error relative to
@@ -496,6 +497,9 @@ def _census_steps():
             w = bench.synthetic_latents(coach.net.decoder, b, 0)
             mask = bench.make_mask(coach, b, 1024, 0, dev) if workload == 3 else None
             yield (f"workload {workload} batch {b}", lambda: coach.train_step(w, mask))
+        if workload == 2:  # the paths the default steps do not take, on the same model set
+            yield ("workload 2 batch 2, deterministic mode", lambda: _deterministic_step(coach, bench.synthetic_latents(coach.net.decoder, 2, 0)))
+            yield ("generator batch 1, train_conv_weights", lambda: _conv_weight_step(coach.net.decoder, bench.synthetic_latents(coach.net.decoder, 1, 0)))
         del coach
         torch.cuda.empty_cache()
     from where2edit_amd.demo_pipeline import invert_and_edit
@@ -504,14 +508,55 @@ def _census_steps():
         yield (f"workload 5 batch {b}", lambda: invert_and_edit(imgs[:b], e4e, g, clip, net, text[:b], att[:b], attention_layer=13))
     del imgs, e4e, g, clip, net
     torch.cuda.empty_cache()
+    yield ("discriminator 1024^2 batch 1, forward and backward", _discriminator_step)
+    torch.cuda.empty_cache()
+
+
+def _deterministic_step(coach, w):
+    """One step in deterministic mode: the unfused activation backward + adjoint blur instead of w2e_blur_adjoint_actbwd."""
+    from where2edit_amd import _lib
+    _lib.set_option("deterministic", "1")
+    try:
+        coach.train_step(w)
+    finally:
+        _lib.set_option("deterministic", os.environ.get("W2E_DETERMINISTIC", "0"))
+
+
+def _conv_weight_step(decoder, w):
+    """Generator forward + backward into the conv weights (stylegan2.train_conv_weights); the decoder is frozen again afterwards."""
+    from where2edit_amd.stylegan2 import freeze_conv_weights, train_conv_weights
+    train_conv_weights(decoder)
+    try:
+        img, _ = decoder([w.detach()], input_is_latent=True, randomize_noise=False)
+        img.square().mean().backward()
+        torch.cuda.synchronize()
+    finally:
+        freeze_conv_weights(decoder)
+        for p in decoder.parameters():
+            p.grad = None
+
+
+def _discriminator_step():
+    import disc64
+    from where2edit_amd.stylegan2 import Discriminator
+    d = Discriminator(1024, 2)
+    d.load_state_dict(disc64.state_dict(1024, 2, salt=3), strict=True)
+    d = d.to("cuda:0")
+    x = disc64.images(1, 1024, salt=3).to("cuda:0").requires_grad_(True)
+    (d(x) * disc64.cotangent(1, salt=3).to("cuda:0")).sum().backward()
+    torch.cuda.synchronize()
 
 
 @pytest.mark.gpu
 def test_census_every_variant_real_steps_pick_is_in_the_matrix():
     """The variants the library picks in real eager steps -- workload 2 at batch 1, 2, 4, 8, workload 3 at batch 2, 8, the workload-5
-    pipeline at batch 1, 4 -- are all among the variants this file tests against float64."""
+    pipeline at batch 1, 4 -- are all among the variants this file tests against float64; and the FIR variants ("upfirdn variant"
+    lines) of the same steps, of a deterministic-mode step, of a conv-weight-gradient step and of a Discriminator forward and
+    backward are all in the matrix of tests/test_gpu_fir_variants.py."""
+    from test_gpu_fir_variants import covered_fir, parse_fir_variants
     from where2edit_amd.profiling import conv_selections
     found, seen = [], {}
+    fir_seen = {}
     for where, fn in _census_steps():
         lines, _ = conv_selections(fn)
         variants = parse_variants(lines)
@@ -519,7 +564,16 @@ def test_census_every_variant_real_steps_pick_is_in_the_matrix():
         for kind, key, layer in variants:
             found.append((kind, key, layer, where))
             seen.setdefault((kind, key), []).append(where)
+        fir = parse_fir_variants(lines)
+        assert fir, f"{where}: no upfirdn variant lines"
+        for key, line in fir:
+            fir_seen.setdefault(key, []).append((where, line))
     for (kind, key), wheres in sorted(seen.items(), key=str):
         print(f"census: {kind} {key}: {len(wheres)} launches, {', '.join(sorted(set(wheres)))}")
+    for key, hits in sorted(fir_seen.items(), key=str):
+        print(f"census: fir {key}: {len(hits)} launches, {', '.join(sorted({wh for wh, _ in hits}))}")
     misses = census_misses(found)
+    covered = covered_fir()
+    misses += [f"fir variant {key} (kernel, act, planar, actbwd, up, down, taps, out_w class) picked by `{hits[0][1]}` at {hits[0][0]} has no entry in "
+               f"the matrix of tests/test_gpu_fir_variants.py: add one" for key, hits in sorted(fir_seen.items(), key=str) if key not in covered]
     assert not misses, "\n".join(misses)

@@ -629,8 +629,8 @@ def _to_planar(t, fill):
 @pytest.mark.parametrize("h,w,separable", [(128, 128, True), (130, 256, True), (96, 128, False), (33, 512, True)])
 @pytest.mark.parametrize("act", [False, True])
 def test_upfirdn_stream_planar_equals_reference_form(h, w, separable, act, w2e_opt):
-    """The streaming 4x4 kernel (wide images) on the UP conv's phase-planar T': same result as the dense generic kernel on the
-    plain image, strips that end mid-way, a non-separable kernel, NaN in the layout's padding (never read)."""
+    """The streaming 4x4 kernel (wide images) on the UP conv's phase-planar T': same result as the LDS-tile kernels (tune_blur = 8:
+    blur4 on this aligned dense source) on the plain image, strips that end mid-way, a non-separable kernel, NaN in the layout's padding (never read)."""
     from where2edit_amd import functional as K
     g = torch.Generator().manual_seed(3 * h + w)
     c = 3
@@ -711,8 +711,18 @@ def test_blur_adjoint_with_fused_activation_backward(h, w, with_noise, w2e_opt):
     gt, sums = torch.full((b, c, 2 * h + 1, 2 * w + 1), float("nan"), device=DEV), torch.full((b, c, 3), float("nan"), device=DEV)
     call("w2e_blur_adjoint_actbwd", ptr(gy), ptr(y), ptr(noise), ptr(k4), ptr(gt), ptr(sums), b * c, 2 * h, 2 * w, 0.2, 2 ** 0.5, stream_ptr())
     assert_close(gt, gt_ref, 2e-6, "adjoint-blurred pre-activation gradient")
-    for i, name in enumerate(("sum gpre*pre", "sum gpre*noise", "sum gpre")):
+    # per plane, relative to the plane's own sum of |terms| (float64, from the definition): an error in a plane of small terms
+    # does not hide below the largest sum.  (tests/test_gpu_fir_variants.py holds both kernels to the float64 sums themselves.)
+    gd, yd = gy.double(), y.double()
+    gp = gd * 2 ** 0.5 * torch.where(yd > 0, 1.0, 0.2)
+    pre = torch.where(yd > 0, yd / 2 ** 0.5, yd / (2 ** 0.5 * 0.2))
+    nz = noise.double() if with_noise else torch.zeros(1, 1, 2 * h, 2 * w, dtype=torch.float64, device=DEV)
+    for i, (name, terms) in enumerate((("sum gpre*pre", gp * pre), ("sum gpre*noise", gp * nz), ("sum gpre", gp))):
         assert_close(sums[..., i] + 1.0, sums_ref[..., i] + 1.0, 2e-5, name)  # (+1: a sum near 0 is compared absolutely)
+        scale = terms.abs().sum((2, 3))
+        err = (sums[..., i].double() - sums_ref[..., i].double()).abs()
+        assert bool((err[scale == 0] == 0).all()), name
+        assert bool((err <= 2e-5 * scale).all()), f"{name}: {float((err / scale.clamp_min(1e-300)).max()):.3e} of a plane's sum of |terms|"
 
 
 @pytest.mark.parametrize("cin,h,with_skip,prefix", [(32, 64, True, 0), (12, 18, False, 0), (512, 8, True, 1), (64, 128, True, 2)])

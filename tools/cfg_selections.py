@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Records which conv tile / split-K factor libw2e.so picks for every w2e_modconv3x3 / w2e_conv3x3 launch of one bench.py
 step (the `tune_print` option: one line per launch on stderr, and one "modconv variant" / "wino_fused variant" line with the
-kernel variant that ran).  The selection depends on the batch, so the file lists the
+kernel variant that ran; the FIR launches of the step appear between them as "upfirdn variant" lines).  The selection depends on the batch, so the file lists the
 steps the bench and the driver really run: workload 2 at batch 4 (BASELINE configs[1]) and at batch 8 (configs[3]'s per-rank
 workload), workload 3 at batch 8 (configs[2]).
 

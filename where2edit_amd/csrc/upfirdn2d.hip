@@ -1,11 +1,15 @@
 // K2: upfirdn2d for gfx950 (replaces models/stylegan2/op/upfirdn2d.py:11-60).
 //
-// Two kernels:
-//   * upfirdn_tile_kernel  -- up=1, down=1 (the 8 Blur calls per forward, the HBM-heavy case:
-//     134 MB in + 134 MB out per image at 1024^2).  64x16 output tile per 256-thread block, the
-//     (16+kh-1) x (64+kw-1) input tile staged once in LDS, 4 outputs per thread, float4 stores,
-//     optional fused demod/noise/bias/LeakyReLU epilogue so the activation is written once.
-//   * upfirdn_generic_kernel -- any up/down/pad/flip (RGB skip up-sampling, Downsample, adjoints).
+// Six kernels, fourteen instantiations (the dispatcher at the end of the file picks one per launch and, with tune_print on, says
+// which in an "upfirdn variant" line; tests/test_gpu_fir_variants.py runs every one of them against float64):
+//   * upfirdn_generic_kernel -- any up / down / pad / flip / tap count <= 16, optional epilogue: up-sampling, > 8 taps, out_w < 32.
+//   * upfirdn_down4_kernel   -- 4x4 taps, up = 1, any down, no epilogue (the adjoint of the RGB-skip Upsample, tiny blurs).
+//   * upfirdn_tile_kernel    -- up = down = 1, out_w >= 32, <= 8 taps per axis but not 4x4: a 64x32 output tile per 256-thread
+//     block, the (32+kh-1) x (64+kw-1) input tile staged once in LDS, optional fused demod/noise/bias/LeakyReLU epilogue.
+//   * upfirdn_tile4_kernel<ACT> -- 4x4, up = down = 1, source rows not 16-byte aligned (odd in_w, an offset x): scalar staging.
+//   * upfirdn_blur4_kernel<ACT, PLANAR> -- 4x4, up = down = 1, aligned dense source or the UP conv's phase-planar source.
+//   * upfirdn_stream4_kernel<ACT, PLANAR> and <false, false, ACTBWD> -- out_w >= 256: no LDS, no barriers (the 8 Blur calls per
+//     forward at up to 1024^2 and their adjoints, the HBM-heavy case: 134 MB in + 134 MB out per image at 1024^2).
 #include <stdlib.h>
 
 #include "common.h"
@@ -346,7 +350,7 @@ __global__ __launch_bounds__(256) void upfirdn_blur4_kernel(UpfirdnParams p, int
 //    of 4, pad_x0 = 2: the adjoint blur): outputs are paired (0,1),(2,3) and the pairs are (w_i, w_i+1), i = 0..5.
 //    A pair that straddles the image's left / right edge is fixed up by a select in the waves that hold such a lane; whole
 //    pairs outside the image, and rows outside it, fall past a descriptor and read as 0.
-//  * Dense source with an odd out_w (in_w + 1): the lane owning the last full group also computes the single last column.
+//  * Dense source with out_w = in_w + 1: the lane owning the last full group also computes the single last column.
 constexpr int SR = 64;  // strip rows per wave (3 halo rows re-read per strip: 4.7 %)
 
 //  * ACTBWD (dense source, the StyledConv backward of an up-sampling layer): the source is read together with the layer's
@@ -503,7 +507,10 @@ __global__ __launch_bounds__(256) void upfirdn_stream4_kernel(UpfirdnParams p, i
     const __amdgpu_buffer_rsrc_t rn = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ACT && p.noise ? p.noise : p.x), (short)0,
                                                                       (ACT && p.noise) ? (int)out_bytes : 0, 0x00020000);
     const bool full4 = ox + 3 < p.out_w;
-    const bool edge5 = !PLANAR && (p.out_w & 3) == 1 && ox + 4 == p.out_w - 1;  // this lane also owns the single last column
+    // this lane also owns the single last column -- only when that column is the one past the source (out_w = in_w + 1): its
+    // fourth tap then lies outside the image and the 7-wide window holds the other three.  A narrower odd output ends on
+    // a ragged group like any other width.
+    const bool edge5 = !PLANAR && (p.out_w & 3) == 1 && p.out_w == p.in_w + 1 && ox + 4 == p.out_w - 1;
     const bool wave_edge5 = !PLANAR && __builtin_amdgcn_ballot_w64(edge5) != 0ull;  // (uniform)
     const unsigned vout = ox < p.out_w ? (unsigned)ox * 4u : OOB;
     // (v*scale + bias + nw*noise) -> lrelu -> *gain  ==  lrelu(v*scale*gain + bias*gain + nw*gain*noise) for gain > 0
@@ -592,7 +599,15 @@ __global__ __launch_bounds__(256) void upfirdn_stream4_kernel(UpfirdnParams p, i
                 for (int c = 0; c < 3; ++c)
                     if (ox + c < p.out_w) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v[c]), ry, vout + 4u * c, srow, 0);
             }
-            if (wave_edge5 && edge5) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v5), ry, vout + 16u, srow, 0);
+            if (wave_edge5 && edge5) {  // the single last column: its own epilogue (its noise value is fetched here: one lane per row)
+                float e5 = v5;
+                if (ACT) {
+                    const float n5 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rn, vout + 16u, srow, 0));
+                    const float e = v5 * e_scale + e_bias + nw * n5;
+                    e5 = fold ? fmaxf(e, e * p.slope) : (e > 0.f ? e : e * p.slope) * p.gain;
+                }
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, e5), ry, vout + 16u, srow, 0);
+            }
         }
     };
 
@@ -764,6 +779,12 @@ __global__ void upfirdn_generic_kernel(UpfirdnParams p, int64_t total) {
     }
 }
 
+// "upfirdn variant ..." (tune_print): the kernel and template flags of one launch
+static void print_variant(const char* kernel, int act, int planar, int actbwd, const UpfirdnParams& p) {
+    fprintf(stderr, "upfirdn variant kernel %s act %d planar %d actbwd %d up %d down %d taps %dx%d %lld %dx%d -> %dx%d\n", kernel, act, planar, actbwd,
+            p.up, p.down, p.kh, p.kw, (long long)p.planes, p.in_h, p.in_w, p.out_h, p.out_w);
+}
+
 }  // namespace w2e
 
 using namespace w2e;
@@ -792,6 +813,11 @@ extern "C" int w2e_upfirdn2d(const float* x, const float* kern, float* y, int64_
     UpfirdnParams p{x, kern, y, planes, in_h, in_w, out_h, out_w, kh, kw, up, down, pad_x0, pad_y0, flip, tune, in_layout,
                     act, out_scale, noise, noise_w, bias, channels > 0 ? channels : 1, slope, gain, nullptr, nullptr};
     hipStream_t s = (hipStream_t)stream;
+    // the variant that runs, printed where it is launched (tests/test_gpu_fir_variants.py keys its matrix and its census on this line)
+    const bool print = options().tune_print != 0;
+    auto variant = [&](const char* kernel, int v_act, int v_planar) {
+        if (print) print_variant(kernel, v_act, v_planar, 0, p);
+    };
     if (up == 1 && down == 1 && out_w >= 32 && kh <= MAX_TILE_K && kw <= MAX_TILE_K) {
         const int tiles_x = (int)ceil_div(out_w, TW), tiles_y = (int)ceil_div(out_h, TH);
         const int64_t n_tiles = planes * tiles_x * tiles_y;
@@ -807,11 +833,12 @@ extern "C" int w2e_upfirdn2d(const float* x, const float* kern, float* y, int64_
                                    (in_layout ? (pad_x0 == 1 && (out_w & 3) == 0 && in_w == out_w + 1)
                                               : (pad_x0 == 2 && (in_w & 3) == 0 && out_w <= in_w + 1));
             if (stream_ok) {
-                const int lanes = (!in_layout && (out_w & 3) == 1) ? out_w / 4 : (int)ceil_div(out_w, 4);  // (a single last column rides on the last full group)
+                const int lanes = (!in_layout && out_w == in_w + 1) ? out_w / 4 : (int)ceil_div(out_w, 4);  // (the single column past the source rides on the last full group)
                 const int col_groups = (int)ceil_div(lanes, 64), strips = (int)ceil_div(out_h, SR);
                 const int64_t waves = planes * col_groups * strips;
                 W2E_REQUIRE(waves < ((int64_t)1 << 31), "upfirdn2d: tensor too large");
                 const unsigned blocks = (unsigned)ceil_div(waves, 4);
+                variant("stream4", act != 0, in_layout);
                 if (in_layout) {
                     if (act) upfirdn_stream4_kernel<true, true><<<blocks, 256, 0, s>>>(p, col_groups, strips);
                     else upfirdn_stream4_kernel<false, true><<<blocks, 256, 0, s>>>(p, col_groups, strips);
@@ -829,6 +856,7 @@ extern "C" int w2e_upfirdn2d(const float* x, const float* kern, float* y, int64_
                 constexpr int PWc = TW + 3, PHc = TH + 3;
                 const size_t lds2 = in_layout ? sizeof(float) * 2 * PHc * 4 * (((PWc + 1) / 2 + 1 + 3) / 4 + 1)
                                               : sizeof(float) * PHc * 4 * ((PWc + 3) / 4 + 1);
+                variant("blur4", act != 0, in_layout);
                 if (in_layout) {
                     if (act) upfirdn_blur4_kernel<true, true><<<g2, 256, lds2, s>>>(p, tiles_x, tiles_y);
                     else upfirdn_blur4_kernel<false, true><<<g2, 256, lds2, s>>>(p, tiles_x, tiles_y);
@@ -837,15 +865,19 @@ extern "C" int w2e_upfirdn2d(const float* x, const float* kern, float* y, int64_
                     else upfirdn_blur4_kernel<false, false><<<g2, 256, lds2, s>>>(p, tiles_x, tiles_y);
                 }
             } else {
+                variant("tile4", act != 0, 0);
                 if (act) upfirdn_tile4_kernel<true><<<grid, 256, lds, s>>>(p, tiles_x, tiles_y, magic);
                 else upfirdn_tile4_kernel<false><<<grid, 256, lds, s>>>(p, tiles_x, tiles_y, magic);
             }
         } else {
+            variant("tile", act != 0, 0);
             upfirdn_tile_kernel<<<grid, 256, lds, s>>>(p, tiles_x, tiles_y, magic);
         }
     } else if (up == 1 && kh == 4 && kw == 4 && !act && !in_layout && planes * in_h * in_w < ((int64_t)1 << 29) && total < ((int64_t)1 << 31)) {
+        variant("down4", 0, 0);
         upfirdn_down4_kernel<<<(unsigned)ceil_div(total, 256), 256, 0, s>>>(p, total);
     } else {
+        variant("generic", act != 0, 0);
         upfirdn_generic_kernel<<<stream_grid(total, 256), 256, 0, s>>>(p, total);
     }
     W2E_LAUNCH_CHECK("upfirdn2d");
@@ -873,6 +905,7 @@ extern "C" int w2e_blur_adjoint_actbwd(const float* gy, const float* y_fwd, cons
     const int col_groups = (int)ceil_div(lanes, 64), strips = (int)ceil_div(h + 1, SR);
     const int64_t waves = planes * col_groups * strips;
     W2E_REQUIRE(waves < ((int64_t)1 << 31), "blur_adjoint_actbwd: tensor too large");
+    if (options().tune_print) print_variant("stream4", 0, 0, 1, p);
     upfirdn_stream4_kernel<false, false, true><<<(unsigned)ceil_div(waves, 4), 256, 0, s>>>(p, col_groups, strips);
     W2E_LAUNCH_CHECK("blur_adjoint_actbwd");
     return 0;

@@ -1,6 +1,6 @@
 """HIP-event timing of individual C-ABI calls on the stream they are launched on (torch's current
 stream).  bench.py uses it to price the dominant kernel inside the timed region; off by default.
-conv_selections(): which conv kernel variant every launch of a piece of work picked."""
+conv_selections(): which conv and FIR kernel variant every launch of a piece of work picked."""
 import os
 import sys
 import tempfile
@@ -54,14 +54,14 @@ def span(name, work=0.0):
     return _Span(name, work) if (_active is not None and _active.enabled) else None
 
 
-SELECTION_PREFIXES = ("modconv mode", "modconv variant", "wino_fused variant", "  ")
+SELECTION_PREFIXES = ("modconv mode", "modconv variant", "wino_fused variant", "upfirdn variant", "  ")
 
 
 def conv_selections(fn):
     """Runs fn() once with the library's `tune_print` option on and returns (lines, wino): `lines` = what w2e_modconv3x3 /
-    w2e_conv3x3 / w2e_wino_fused printed to stderr, in launch order ("modconv mode ..." with its "  lds-dma ..." / "  bf16x3 ..."
-    lines, "modconv variant ...", "wino_fused variant ..."), `wino` = the lines of the Winograd forms chosen on the Python side
-    (functional.WINO_LOG).  tools/cfg_selections.py and the coverage census in tests/test_gpu_conv_variants.py both use it."""
+    w2e_conv3x3 / w2e_wino_fused / w2e_upfirdn2d / w2e_blur_adjoint_actbwd printed to stderr, in launch order ("modconv mode ..." with
+    its "  lds-dma ..." / "  bf16x3 ..." lines, "modconv variant ...", "wino_fused variant ...", "upfirdn variant ..."), `wino` = the lines of the Winograd forms chosen on the Python side
+    (functional.WINO_LOG).  tools/cfg_selections.py and the coverage census in tests/test_gpu_conv_variants.py (conv and FIR variants) both use it."""
     from . import _lib
     from . import functional as K
     torch.cuda.synchronize()
