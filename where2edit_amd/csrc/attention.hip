@@ -2,15 +2,9 @@
 // the 576->1 StyledConv + sigmoid, and the per-cluster pooling + threshold + 5x5 gaussian.  All HBM/latency-bound fp32
 // VALU work on at most [B,576,64,64]-sized data; no MFMA on purpose (N = 32 and N = 1 outputs, 6.4 GFLOP per batch of 4).
 #include "../../include/w2e_attention.h"
-#include "common.h"
+#include "device.h"
 
 namespace w2e {
-
-__device__ __forceinline__ float wave_sum64(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // ---------------------------------------------------------------------------------------- cluster assignment
 // A workgroup owns 64 pixels; its 4 waves split the channel range (wave w: channels [w*C/4, (w+1)*C/4), the 2P analytic
@@ -115,7 +109,7 @@ __global__ __launch_bounds__(256) void cluster_accumulate_kernel(const float* __
     }
 #pragma unroll
     for (int k = 0; k < KP; ++k) {
-        const float t = wave_sum64(acc[k]);
+        const float t = wave_sum(acc[k]);
         if (lane == 0) red[wave][k] = t;
     }
     __syncthreads();
@@ -272,7 +266,7 @@ __global__ __launch_bounds__(256) void cluster_pool_kernel(const float* __restri
         float s = 0.f, n = 0.f;
         for (int p = threadIdx.x; p < npix; p += 256)
             if (cluster_of(p) == k) s += e[p], n += 1.f;
-        s = wave_sum64(s), n = wave_sum64(n);
+        s = wave_sum(s), n = wave_sum(n);
         if (lane == 0) part[wave][0] = s, part[wave][1] = n;
         __syncthreads();
         if (threadIdx.x == 0) {

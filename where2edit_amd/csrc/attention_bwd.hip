@@ -6,15 +6,9 @@
 // activations -- the expensive, strided gather from maps of up to 1024^2 -- are read exactly once per backward, by the contraction
 // G[b,i,o] = sum_p feat[b,i,src(p)] * g_m[b,o,p].  Re-evaluating the sums instead would read every activation twice.
 #include "../../include/w2e_attention.h"
-#include "common.h"
+#include "device.h"
 
 namespace w2e {
-
-__device__ __forceinline__ float bwd_wave_sum64(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 constexpr float SQRT2 = 1.4142135623730951f;
 constexpr int TILE_VALS = 97;  // per (source, sample, 256-pixel tile): g_lcoef[32], g_bias[32], g_demod[32], g_noise_w
@@ -50,7 +44,7 @@ __global__ __launch_bounds__(256) void att_bwd_head_kernel(const AttBwdLaunch L)
         L.gz[e] = gv * dl;
         a0 += gu, a1 += gv, a2 += gv * nl, a3 += gv * z;
     }
-    a0 = bwd_wave_sum64(a0), a1 = bwd_wave_sum64(a1), a2 = bwd_wave_sum64(a2), a3 = bwd_wave_sum64(a3);
+    a0 = wave_sum(a0), a1 = wave_sum(a1), a2 = wave_sum(a2), a3 = wave_sum(a3);
     if (lane == 0) red[wave][0] = a0, red[wave][1] = a1, red[wave][2] = a2, red[wave][3] = a3;
     __syncthreads();
     if (threadIdx.x < 4) {
@@ -90,10 +84,10 @@ __global__ __launch_bounds__(256) void att_bwd_pixel_kernel(const AttBwdLaunch L
         const float gpre = gz * lcoef[o] * SQRT2 * (pre > 0.f ? 1.f : 0.2f);
         if (live) L.gm[base + (int64_t)o * npix] = gpre * dcoef[o];
         gsum += gpre;
-        const float r0 = bwd_wave_sum64(gz * a), r1 = bwd_wave_sum64(gpre), r2 = bwd_wave_sum64(gpre * m);
+        const float r0 = wave_sum(gz * a), r1 = wave_sum(gpre), r2 = wave_sum(gpre * m);
         if (lane == 0) red[wave][o] = r0, red[wave][32 + o] = r1, red[wave][64 + o] = r2;
     }
-    const float r3 = bwd_wave_sum64(gsum * nr);
+    const float r3 = wave_sum(gsum * nr);
     if (lane == 0) red[wave][96] = r3;
     __syncthreads();
     if (threadIdx.x < TILE_VALS) {
@@ -306,7 +300,7 @@ __global__ __launch_bounds__(256) void cluster_pool_bwd_kernel(const float* __re
         float sg = 0.f;
         for (int p = threadIdx.x; p < npix; p += 256)
             if (cluster_of(p) == k) sg += ga[p];
-        sg = bwd_wave_sum64(sg);
+        sg = wave_sum(sg);
         if (lane == 0) part[wave] = sg;
         __syncthreads();
         if (threadIdx.x == 0) {

@@ -4,7 +4,7 @@
 //   mbstd      the minibatch-stddev channel (model.py:690-698): one extra channel per sample, the mean over C*H*W of
 //              sqrt(var over the group + 1e-8), appended behind the C channels (torch.cat([out, stddev], 1)).
 // No atomics, no memsets: every reduction runs in a fixed order, so every result is bit-reproducible and capturable.
-#include "common.h"
+#include "device.h"
 
 namespace w2e {
 
@@ -14,12 +14,6 @@ constexpr float kSqrt2 = 1.41421356237309504880f;
 constexpr int FR_PPT = 4;                  // pixels per thread of the fromRGB backward
 constexpr int FR_PPB = 256 * FR_PPT;       // pixels per workgroup (one partial row per workgroup)
 constexpr int FR_MAX_C = 512;
-
-__device__ __forceinline__ float wave_sum_disc(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // y[b,o,p] = lrelu(scale * sum_i w[o,i] x[b,i,p] + bias[o], 0.2) * sqrt2; one thread per pixel, every output channel.
 __global__ __launch_bounds__(256) void fromrgb_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
@@ -87,10 +81,10 @@ __global__ __launch_bounds__(256) void fromrgb_bwd_kernel(const float* __restric
             s3 += g;
         }
         if (part) {
-            s0 = wave_sum_disc(s0);
-            s1 = wave_sum_disc(s1);
-            s2 = wave_sum_disc(s2);
-            s3 = wave_sum_disc(s3);
+            s0 = wave_sum(s0);
+            s1 = wave_sum(s1);
+            s2 = wave_sum(s2);
+            s3 = wave_sum(s3);
             if (lane == 0) red[wv][o] = make_float4(s0, s1, s2, s3);
         }
     }
@@ -147,7 +141,7 @@ __global__ __launch_bounds__(256) void fromrgb_finish_kernel(const float4* __res
 
 __device__ float block_sum_256(float v, float* red) {
     const int tid = threadIdx.x;
-    v = wave_sum_disc(v);
+    v = wave_sum(v);
     __syncthreads();
     if ((tid & 63) == 0) red[tid >> 6] = v;
     __syncthreads();

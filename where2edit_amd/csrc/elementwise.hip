@@ -1,6 +1,6 @@
 // HBM-bound kernels of the Where2edit hot path for gfx950: fused bias/noise/LeakyReLU (K3),
 // region-attention blend (K6), CLIP preprocessing (K5).  Vectorised 16 B/lane, grid-strided.
-#include "common.h"
+#include "device.h"
 
 namespace w2e {
 
@@ -72,12 +72,6 @@ __global__ void bias_act_bwd_kernel(const float* __restrict__ gy, const float* _
         for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += step)
             gx[e] = gy[e] * gain * (y[e] > 0.f ? 1.f : slope);
     }
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
 }
 
 // One (outer,channel) row of `inner` elements is split over `splits` blocks; each block reduces its

@@ -2,7 +2,7 @@
 // pooling and gating, the residual joins and their adjoints.  All HBM-bound, grid-strided; the 3x3 convolutions run on
 // the MFMA engine of modconv.hip (w2e_conv3x3).
 #include "../../include/w2e_irse.h"
-#include "common.h"
+#include "device.h"
 
 namespace w2e {
 
@@ -54,12 +54,6 @@ __global__ void affine_act_bwd_kernel(const float* __restrict__ gy, const float*
     }
 }
 
-__device__ __forceinline__ float wave_sum_irse(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // one wave per (b,c) plane, 4 planes per block; lanes stride the plane (float4 when aligned)
 __global__ __launch_bounds__(256) void channel_sums_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                            float* __restrict__ sums, int64_t planes, int64_t hw) {
@@ -84,7 +78,7 @@ __global__ __launch_bounds__(256) void channel_sums_kernel(const float* __restri
     } else {
         for (int64_t p = lane; p < hw; p += 64) acc += yp ? xp[p] * yp[p] : xp[p];
     }
-    acc = wave_sum_irse(acc);
+    acc = wave_sum(acc);
     if (lane == 0) sums[plane] = acc;
 }
 
@@ -104,7 +98,7 @@ __global__ __launch_bounds__(256) void se_gate_fwd_kernel(const float* __restric
         const float* w = fc1 + (int64_t)r * C;
         float acc = 0.f;
         for (int c = lane; c < C; c += 64) acc += w[c] * pooled[c];
-        acc = wave_sum_irse(acc);
+        acc = wave_sum(acc);
         if (lane == 0) {
             acc = acc > 0.f ? acc : 0.f;
             hid[r] = acc;
@@ -138,7 +132,7 @@ __global__ __launch_bounds__(256) void se_gate_bwd_kernel(const float* __restric
     for (int r = wave; r < R; r += 4) {
         float acc = 0.f;
         for (int c = lane; c < C; c += 64) acc += fc2[(int64_t)c * R + r] * d2[c];
-        acc = wave_sum_irse(acc);
+        acc = wave_sum(acc);
         if (lane == 0) dh[r] = hidden[(int64_t)b * R + r] > 0.f ? acc : 0.f;
     }
     __syncthreads();

@@ -17,7 +17,7 @@
 // a register and flushed when the cluster changes.  Pixels in order, no atomics: the result is a function of the data and the
 // grid size only.
 #include "../../include/w2e_attention.h"
-#include "common.h"
+#include "device.h"
 
 namespace w2e {
 namespace {
@@ -27,12 +27,6 @@ constexpr int KM_TILE = 128;     // pixels per tile
 constexpr int KM_FLY = 16;       // channel planes in flight per wave
 
 enum { KM_ASSIGN = 0, KM_STEP = 1, KM_SEED = 2 };
-
-__device__ __forceinline__ float km_wave_sum64(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 __host__ __device__ inline int64_t km_lds_floats(int D, int KP, int K, int mode) {
     return (int64_t)D * KP + 6 * 64 * KP + KM_TILE + 2 * KP + (mode == KM_STEP ? (int64_t)K * (D + 1) : 0);
@@ -194,7 +188,7 @@ __global__ __launch_bounds__(KM_THREADS) void kmeans_pass_kernel(const float* __
     if (q == 0) {
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
-            const float s = km_wave_sum64(tot[t]);
+            const float s = wave_sum(tot[t]);
             if (lane == 0) red[half * KP + t] = s;
         }
     }

@@ -3,20 +3,14 @@
 //                 exp(logit_scale), optionally as the loss's similarity 1 - logits/100; forward and the gradient to the image features
 //   step_loss     mapper/training/coach.py:223-245: clip_lambda * mean(similarity) + l2_lambda * MSE(w_hat, w); forward and backward
 // [B, T] / [B, 18, 512]-sized work: nothing here is bound by anything but launch count.  Fixed reduction orders (bit-reproducible).
-#include "common.h"
+#include "device.h"
 #include "../../include/w2e_vit.h"
 
 namespace w2e {
 
-__device__ __forceinline__ float lt_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // block reduction of one value over 256 threads (4 waves), result to every thread
 __device__ __forceinline__ float lt_block_sum(float v, float* sm) {
-    v = lt_wave_sum(v);
+    v = wave_sum(v);
     __syncthreads();  // (sm may still be read from a previous reduction)
     if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
     __syncthreads();
@@ -85,7 +79,7 @@ __global__ __launch_bounds__(1024) void step_loss_fwd_kernel(const float* __rest
         const float d = w_hat[i] - w[i];
         q += d * d;
     }
-    a = lt_wave_sum(a), q = lt_wave_sum(q);
+    a = wave_sum(a), q = wave_sum(q);
     if ((threadIdx.x & 63) == 0) sm[0][threadIdx.x >> 6] = a, sm[1][threadIdx.x >> 6] = q;
     __syncthreads();
     if (threadIdx.x == 0) {

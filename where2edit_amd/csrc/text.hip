@@ -4,15 +4,11 @@
 //   attn_causal     softmax(QK^T/8 + triu(-inf, 1)) V per (batch, head), L <= 96, on v_mfma_f32_32x32x2_f32
 //   text_pool       the EOT row (first argmax of the tokens) of the last block's output, summed from its slabs, through ln_final
 // No atomics, no memsets: every output element is written by exactly one lane, sums run in a fixed order.
-#include "common.h"
+#include "device.h"
 #include "../../include/w2e_vit.h"
 
 namespace w2e {
 namespace text {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ float4 add4(const float4 a, const float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 
 __device__ __forceinline__ int64_t token_at(const void* tokens, int token_bytes, int64_t i) {
     return token_bytes == 8 ? reinterpret_cast<const int64_t*>(tokens)[i] : (int64_t)reinterpret_cast<const int32_t*>(tokens)[i];
@@ -44,87 +40,9 @@ __global__ void text_embed_kernel(const void* __restrict__ tokens, int token_byt
 // groups over any 16 consecutive rows: the b128 operand fetches are conflict-free).  S = QK^T has a 3x3 grid of 32x32 blocks of which
 // the six on and below the diagonal are live: wave w owns one of them; the three above it are never computed.  O = PV has
 // 3x2 blocks of 32x32: wave w owns block (w>>1, w&1) and contracts only over the columns j < 32*(row block + 1).  k-slot
-// convention as in vit2.hip: lane-half h, group g, component c <-> k = 8g + 4h + c.
+// convention of device.h: lane-half h, group g, component c <-> k = 8g + 4h + c.  Thread t of the 384 stages columns 4*(t&15) .. +3 of
+// rows (t>>4) + 24q (load_heads<3, 2, 24, CS>); the softmax runs four adjacent lanes per row, as vit2.hip's softmax_rows.
 constexpr int CL = 96, CS = 68, PS = 100, CT = 384;
-
-// acc += A_rows . B_rows^T over 64 k: out[i][j] = sum_k A[i][k] B[j][k]
-__device__ __forceinline__ void mm_rows_rows(f32x16& acc, const float* A, const float* B, int i0, int j0, int j, int half) {
-    const float4* ar = reinterpret_cast<const float4*>(A + (i0 + j) * CS) + half;
-    const float4* br = reinterpret_cast<const float4*>(B + (j0 + j) * CS) + half;
-#pragma unroll
-    for (int g = 0; g < 8; ++g) {
-        const float4 a4 = ar[2 * g], b4 = br[2 * g];
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, b4.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b4.y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b4.z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, b4.w, acc, 0, 0, 0);
-    }
-}
-// acc += A . B over k < 8 * groups: out[i][n] = sum_k A[i][k] B[k][n]   (A = P [96][PS] row-major b128; B = V [96][CS] read down
-// its rows, lanes along n)
-__device__ __forceinline__ void mm_rows_cols(f32x16& acc, const float* A, const float* B, int i0, int n0, int j, int half, int groups) {
-    const float4* ar = reinterpret_cast<const float4*>(A + (i0 + j) * PS) + half;
-    const float* bc = B + n0 + j;
-    for (int g = 0; g < groups; ++g) {
-        const float4 a4 = ar[2 * g];
-        const int k = 8 * g + 4 * half;
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, bc[(k + 0) * CS], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, bc[(k + 1) * CS], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, bc[(k + 2) * CS], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, bc[(k + 3) * CS], acc, 0, 0, 0);
-    }
-}
-
-// Q, K, V of head h for the L rows of one sequence (a [B*L, 3*H*64] matrix given as nsplit slabs + bias) -> LDS [96][CS],
-// rows >= L zero.  Thread: columns d..d+3, rows t0 + 24q.  Slab outermost with CH slabs' loads in flight, added in ascending
-// slab order (the order of vit2.hip's load_heads).
-template <int CH>
-__device__ __forceinline__ void load_qkv(const float* src, int nsplit, int64_t slab, const float* bias, int64_t row0, int ld,
-                                         const int (&col)[3], int L, float* const (&dst)[3]) {
-    float4 v[3][4];
-    const int d = (threadIdx.x & 15) * 4, t0 = threadIdx.x >> 4;  // t0 in [0, 24)
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[a][q] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int base = 0; base < nsplit; base += CH) {
-        float4 w[CH][3][4];
-#pragma unroll
-        for (int c = 0; c < CH; ++c)
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int t = t0 + 24 * q;
-                    w[c][a][q] = (base + c < nsplit && t < L)
-                                     ? *reinterpret_cast<const float4*>(src + (base + c) * slab + (row0 + t) * ld + col[a] + d)
-                                     : make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-#pragma unroll
-        for (int c = 0; c < CH; ++c)
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) v[a][q] = add4(v[a][q], w[c][a][q]);
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float4 bv = bias ? *reinterpret_cast<const float4*>(bias + col[a] + d) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int t = t0 + 24 * q;
-            *reinterpret_cast<float4*>(dst[a] + t * CS + d) = t < L ? add4(v[a][q], bv) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    }
-}
-
-// Four adjacent lanes per row (as vit2.hip's softmax_rows): the row reductions are two DPP quad permutes.
-__device__ __forceinline__ float quad_xor1(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, false));  // quad_perm [1,0,3,2]
-}
-__device__ __forceinline__ float quad_xor2(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, false));  // quad_perm [2,3,0,1]
-}
 
 __global__ __launch_bounds__(CT) void attn_causal_fwd_kernel(const float* __restrict__ qkv, int nsplit, int64_t slab,
                                                              const float* __restrict__ bias, float* __restrict__ out, int L, int H,
@@ -140,7 +58,7 @@ __global__ __launch_bounds__(CT) void attn_causal_fwd_kernel(const float* __rest
     {
         const int cols[3] = {h * 64, (H + h) * 64, (2 * H + h) * 64};
         float* const dsts[3] = {q, k, v};
-        load_qkv<2>(qkv, nsplit, slab, bias, (int64_t)b * L, ld, cols, L, dsts);
+        load_heads<3, 2, 24, CS>(qkv, nsplit, slab, bias, (int64_t)b * L, ld, cols, L, dsts);
     }
     __syncthreads();
     // S: live block (bi, bj), bj <= bi, of the lower triangle; a block row at or past L has no row to produce
@@ -149,11 +67,9 @@ __global__ __launch_bounds__(CT) void attn_causal_fwd_kernel(const float* __rest
         const int bj = wave - bi * (bi + 1) / 2;
         if (bi * 32 < L) {
             f32x16 acc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-            mm_rows_rows(acc, q, k, bi * 32, bj * 32, j, half);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) p[(bi * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * PS + bj * 32 + j] = acc[r] * 0.125f;
+            acc_zero(acc);
+            mm_rows_rows<CS, CS>(acc, q, k, bi * 32, bj * 32, j, half);
+            acc_to_lds<PS>(acc, p, bi * 32, bj * 32, j, half, 0.125f);
         }
     }
     __syncthreads();
@@ -169,17 +85,14 @@ __global__ __launch_bounds__(CT) void attn_causal_fwd_kernel(const float* __rest
                 x[u] = jj <= i ? p[i * PS + jj] : -3.0e38f;
                 mx = fmaxf(mx, x[u]);
             }
-            mx = fmaxf(mx, quad_xor1(mx));
-            mx = fmaxf(mx, quad_xor2(mx));
+            mx = quad_max(mx);
             float sum = 0.f;
 #pragma unroll
             for (int u = 0; u < CL / 4; ++u) {
                 x[u] = (4 * u + c <= i) ? __expf(x[u] - mx) : 0.f;
                 sum += x[u];
             }
-            sum += quad_xor1(sum);
-            sum += quad_xor2(sum);
-            const float inv = 1.f / sum;
+            const float inv = 1.f / quad_sum(sum);
             const int width = 32 * (i / 32 + 1);
 #pragma unroll
             for (int u = 0; u < CL / 4; ++u)
@@ -191,16 +104,15 @@ __global__ __launch_bounds__(CT) void attn_causal_fwd_kernel(const float* __rest
     const int bi = wave >> 1, dj = wave & 1;
     if (bi * 32 >= L) return;
     f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    mm_rows_cols(acc, p, v, bi * 32, dj * 32, j, half, 4 * (bi + 1));
+    acc_zero(acc);
+    mm_rows_cols<PS, CS>(acc, p, v, bi * 32, dj * 32, j, half, 4 * (bi + 1));
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int i = bi * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        const int i = bi * 32 + acc_row(r, half);
         if (i >= L) continue;
         const int64_t m = (int64_t)b * L + i;
         const int n = h * 64 + dj * 32 + j;
-        if (out_mpad > 0) out[((int64_t)(n >> 2) * out_mpad + m) * 4 + (n & 3)] = acc[r];  // K-quad-major (vit3.hip): the out-projection's A operand
+        if (out_mpad > 0) out[kq_index(m, n, out_mpad)] = acc[r];  // K-quad-major: the out-projection's A operand
         else out[m * (H * 64) + n] = acc[r];
     }
 }

@@ -2,7 +2,7 @@
 // skip, in one pass over the feature map (replaces models/stylegan2/model.py:343-362 = grouped 1x1
 // F.conv2d + bias add + upfirdn2d(up=2) + add).  N=3 is a per-pixel dot product, HBM-bound (the
 // feature map is read exactly once), so this is a wavefront-FMA kernel, not MFMA.
-#include "common.h"
+#include "device.h"
 
 namespace w2e {
 
@@ -104,12 +104,6 @@ __global__ __launch_bounds__(256) void torgb_fwd_kernel(const float* __restrict_
     }
 }
 
-__device__ __forceinline__ float wave_sum64(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // One wave per (b, channel i, pixel split): gx[b,i,p] = sum_c wmod[b,c,i]*gy[b,c,p] and
 // gwmod[b,c,i] (+)= sum_p x[b,i,p]*gy[b,c,p].  The 4 waves of a block take 4 consecutive channels of the
 // same pixel range so their gy reads share L1.  ACC: gx = gx_acc + (that sum) -- the gradient that reached x through its
@@ -187,14 +181,14 @@ __global__ __launch_bounds__(256) void torgb_bwd_kernel(const float* __restrict_
         }
     }
     if (ACTB) {
-        t_pre = wave_sum64(t_pre), t_noise = wave_sum64(t_noise), t_sum = wave_sum64(t_sum);
+        t_pre = wave_sum(t_pre), t_noise = wave_sum(t_noise), t_sum = wave_sum(t_sum);
         if (lane == 0) {
             float* d3 = sums3 + ((int64_t)b * cin + i) * 3;
             if (splits == 1) d3[0] = t_pre, d3[1] = t_noise, d3[2] = t_sum;
             else atomicAdd(d3, t_pre), atomicAdd(d3 + 1, t_noise), atomicAdd(d3 + 2, t_sum);
         }
     }
-    s0 = wave_sum64(s0), s1 = wave_sum64(s1), s2 = wave_sum64(s2);
+    s0 = wave_sum(s0), s1 = wave_sum(s1), s2 = wave_sum(s2);
     if (lane == 0) {
         if (style) {
             const float g = wmod[i] * s0 + wmod[cin + i] * s1 + wmod[2 * cin + i] * s2;

@@ -3,7 +3,7 @@
 // with relu2_2's ReLU mask folded into its gradient.  All three are memory-bound; the 3x3 convolutions run on
 // w2e_conv3x3 (modconv.hip / the Winograd forms).
 #include "../../include/w2e_irse.h"
-#include "common.h"
+#include "device.h"
 
 namespace w2e {
 
@@ -125,15 +125,9 @@ __global__ void maxpool2x2_bwd_scalar_kernel(const float* __restrict__ g, const 
 
 constexpr int MSE_BLOCK = 256;
 
-__device__ __forceinline__ float wave_sum_vgg(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // Fixed-order block sum (wave shuffles, then wave 0 over the 4 wave sums); the result is valid in thread 0.
 __device__ __forceinline__ float block_sum_vgg(float v, float* sm) {
-    v = wave_sum_vgg(v);
+    v = wave_sum(v);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) sm[wave] = v;
     __syncthreads();

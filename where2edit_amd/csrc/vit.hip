@@ -3,18 +3,10 @@
 // attention core fwd+bwd (one workgroup per (batch, head), everything in LDS).
 #include <stdlib.h>
 
-#include "common.h"
+#include "device.h"
 #include "../../include/w2e_vit.h"
 
 namespace w2e {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ float quick_gelu(float x) { return x / (1.f + __expf(-1.702f * x)); }
-__device__ __forceinline__ float quick_gelu_grad(float x) {
-    const float s = 1.f / (1.f + __expf(-1.702f * x));
-    return s * (1.f + 1.702f * x * (1.f - s));
-}
 
 // ------------------------------------------------------------------------------------------ GEMM
 // M = 50*batch rows is a skinny GEMM: a handful of tiles, each a long dependent chain of K-steps whose cost is one
@@ -211,14 +203,14 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmParams p) {
     float rs[16], ax[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        const int m = m0 + wm * 32 + acc_row(r, half);
         const int64_t ci = (int64_t)(m < p.m ? m : 0) * p.ldc + n;
         rs[r] = (p.residual && first) ? p.residual[ci] : 0.f;
         ax[r] = p.aux ? p.aux[ci] : 0.f;
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        const int m = m0 + wm * 32 + acc_row(r, half);
         if (m >= p.m) continue;
         const int64_t ci = (int64_t)m * p.ldc + n;
         float v = acc[r] + bs + rs[r];
@@ -229,12 +221,6 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmParams p) {
 }
 
 // ------------------------------------------------------------------------------------------ LayerNorm
-__device__ __forceinline__ float wave_sum_ln(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 constexpr int LN_MAX_PER_LANE = 32;  // dim <= 2048
 
 // The ViT widths (dim = 256 * T4: 768 -> T4 = 3): ONE wave per row and per workgroup (rows = 50 * batch workgroups spread
@@ -256,14 +242,14 @@ __global__ __launch_bounds__(64) void layernorm_fwd_vec_kernel(const float* __re
     float s = 0.f;
 #pragma unroll
     for (int t = 0; t < T4; ++t) s += (v[t].x + v[t].y) + (v[t].z + v[t].w);
-    const float mean = wave_sum_ln(s) / dim;
+    const float mean = wave_sum(s) / dim;
     float q = 0.f;
 #pragma unroll
     for (int t = 0; t < T4; ++t) {
         v[t].x -= mean, v[t].y -= mean, v[t].z -= mean, v[t].w -= mean;
         q += (v[t].x * v[t].x + v[t].y * v[t].y) + (v[t].z * v[t].z + v[t].w * v[t].w);
     }
-    const float rstd = rsqrtf(wave_sum_ln(q) / dim + eps);
+    const float rstd = rsqrtf(wave_sum(q) / dim + eps);
     float4* yr = reinterpret_cast<float4*>(y + row * dim);
 #pragma unroll
     for (int t = 0; t < T4; ++t)
@@ -297,8 +283,8 @@ __global__ __launch_bounds__(64) void layernorm_bwd_vec_kernel(const float* __re
         s1 += (gg[t].x + gg[t].y) + (gg[t].z + gg[t].w);
         s2 += (gg[t].x * xh[t].x + gg[t].y * xh[t].y) + (gg[t].z * xh[t].z + gg[t].w * xh[t].w);
     }
-    s1 = wave_sum_ln(s1) / dim;
-    s2 = wave_sum_ln(s2) / dim;
+    s1 = wave_sum(s1) / dim;
+    s2 = wave_sum(s2) / dim;
     float4* out = reinterpret_cast<float4*>(gx + row * dim);
 #pragma unroll
     for (int t = 0; t < T4; ++t)
@@ -323,7 +309,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
         v[t] = c < dim ? xr[c] : 0.f;
         s += v[t];
     }
-    const float mean = wave_sum_ln(s) / dim;
+    const float mean = wave_sum(s) / dim;
     float q = 0.f;
 #pragma unroll
     for (int t = 0; t < LN_MAX_PER_LANE; ++t) {
@@ -331,7 +317,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
         const float d = c < dim ? v[t] - mean : 0.f;
         q += d * d;
     }
-    const float rstd = rsqrtf(wave_sum_ln(q) / dim + eps);
+    const float rstd = rsqrtf(wave_sum(q) / dim + eps);
 #pragma unroll
     for (int t = 0; t < LN_MAX_PER_LANE; ++t) {
         const int c = lane + 64 * t;
@@ -360,8 +346,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
         s1 += gg[t];
         s2 += gg[t] * xh[t];
     }
-    s1 = wave_sum_ln(s1) / dim;
-    s2 = wave_sum_ln(s2) / dim;
+    s1 = wave_sum(s1) / dim;
+    s2 = wave_sum(s2) / dim;
 #pragma unroll
     for (int t = 0; t < LN_MAX_PER_LANE; ++t) {
         const int c = lane + 64 * t;

@@ -6,34 +6,15 @@
 //   ln_bwd (partial) gx = LN'(sum_s gy_s) + add
 //   reduce_gelu      the QuickGELU pair / its derivative on a sum of slabs
 //   attn v2          softmax(QK^T/8)V per (batch, head) on v_mfma_f32_32x32x2_f32, QKV read as a sum of split-K slabs + bias
-#include "common.h"
+#include "device.h"
 #include "../../include/w2e_vit.h"
 
 namespace w2e {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(3))) char lds_char;
 
-__device__ __forceinline__ float quick_gelu2(float x) { return x / (1.f + __expf(-1.702f * x)); }
-__device__ __forceinline__ float quick_gelu_grad2(float x) {
-    const float s = 1.f / (1.f + __expf(-1.702f * x));
-    return s * (1.f + 1.702f * x * (1.f - s));
-}
-
 // ------------------------------------------------------------------------------------------ reduce + LayerNorm
-__device__ __forceinline__ float wave_sum2(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max2(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-__device__ __forceinline__ float4 add4(const float4 a, const float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-
 // x = sum_s part[s] (+ bias) (+ residual), written to x_out;  y = LayerNorm(x) * gamma + beta (y may be null: sum only).
 // One wave per row, dim = 256 * T4.  The slabs are added in ascending s: deterministic.
 template <int T4>
@@ -74,14 +55,14 @@ __global__ __launch_bounds__(64) void reduce_ln_fwd_kernel(const float* __restri
     float sm = 0.f;
 #pragma unroll
     for (int t = 0; t < T4; ++t) sm += (v[t].x + v[t].y) + (v[t].z + v[t].w);
-    const float mean = wave_sum2(sm) / dim;
+    const float mean = wave_sum(sm) / dim;
     float q = 0.f;
 #pragma unroll
     for (int t = 0; t < T4; ++t) {
         v[t].x -= mean, v[t].y -= mean, v[t].z -= mean, v[t].w -= mean;
         q += (v[t].x * v[t].x + v[t].y * v[t].y) + (v[t].z * v[t].z + v[t].w * v[t].w);
     }
-    const float rstd = rsqrtf(wave_sum2(q) / dim + eps);
+    const float rstd = rsqrtf(wave_sum(q) / dim + eps);
 #pragma unroll
     for (int t = 0; t < T4; ++t) {
         const float4 g = reinterpret_cast<const float4*>(gamma)[lane + 64 * t], bt = reinterpret_cast<const float4*>(beta)[lane + 64 * t];
@@ -128,8 +109,8 @@ __global__ __launch_bounds__(64) void ln_bwd_part_kernel(const float* __restrict
         s1 += (gg[t].x + gg[t].y) + (gg[t].z + gg[t].w);
         s2 += (gg[t].x * xh[t].x + gg[t].y * xh[t].y) + (gg[t].z * xh[t].z + gg[t].w * xh[t].w);
     }
-    s1 = wave_sum2(s1) / dim;
-    s2 = wave_sum2(s2) / dim;
+    s1 = wave_sum(s1) / dim;
+    s2 = wave_sum(s2) / dim;
 #pragma unroll
     for (int t = 0; t < T4; ++t) {
         const float4 ad = add ? reinterpret_cast<const float4*>(add + row * dim)[lane + 64 * t] : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -161,12 +142,12 @@ __global__ void reduce_gelu_kernel(const float* __restrict__ part, int nsplit, i
             reinterpret_cast<float4*>(h)[q] = v;
             // mpad > 0: the GEMM operand (g in mode 0, the gradient in mode 1) is written K-quad-major, P[quad][row] (vit3.hip)
             const int64_t pq = mpad > 0 ? (q % (n >> 2)) * mpad + q / (n >> 2) : q;
-            reinterpret_cast<float4*>(g)[pq] = make_float4(quick_gelu2(v.x), quick_gelu2(v.y), quick_gelu2(v.z), quick_gelu2(v.w));
+            reinterpret_cast<float4*>(g)[pq] = make_float4(quick_gelu(v.x), quick_gelu(v.y), quick_gelu(v.z), quick_gelu(v.w));
         } else {
             const float4 a = reinterpret_cast<const float4*>(aux)[q];
             const int64_t pq = mpad > 0 ? (q % (n >> 2)) * mpad + q / (n >> 2) : q;
-            reinterpret_cast<float4*>(h)[pq] = make_float4(v.x * quick_gelu_grad2(a.x), v.y * quick_gelu_grad2(a.y), v.z * quick_gelu_grad2(a.z),
-                                                           v.w * quick_gelu_grad2(a.w));
+            reinterpret_cast<float4*>(h)[pq] = make_float4(v.x * quick_gelu_grad(a.x), v.y * quick_gelu_grad(a.y), v.z * quick_gelu_grad(a.z),
+                                                           v.w * quick_gelu_grad(a.w));
         }
     }
 }
@@ -175,122 +156,13 @@ __global__ void reduce_gelu_kernel(const float* __restrict__ part, int nsplit, i
 // One workgroup (4 waves) per (batch, head); L <= 64 tokens padded to 64, head dim 64.  Q, K, V (and dO, P, dS) live in LDS
 // as [64][AS] rows, AS = 68 floats (16-B aligned rows, consecutive rows 4 banks apart: the b128 operand fetches of 16
 // consecutive rows hit 16 different bank groups).  Every contraction is 64x64x64 on v_mfma_f32_32x32x2_f32: wave w owns the
-// 32x32 output block (w>>1, w&1).  k-slot convention (same for both operands): lane-half h, group g, component c <-> k =
-// 8g + 4h + c.
+// 32x32 output block (w>>1, w&1).  The contractions, the slab-summing loader and the k-slot convention are device.h's, instantiated
+// for AS-float rows on both operands and 16 rows per staging pass.
 constexpr int AL = 64, AS = 68;
-
-// acc += A_rows . B_rows^T : out[i][j] = sum_k A[i][k] B[j][k]   (both operands row-major, k along the row: b128 fetches)
-__device__ __forceinline__ void mm_rows_rows(f32x16& acc, const float* A, const float* B, int i0, int j0, int j, int half) {
-    const float4* ar = reinterpret_cast<const float4*>(A + (i0 + j) * AS) + half;
-    const float4* br = reinterpret_cast<const float4*>(B + (j0 + j) * AS) + half;
-#pragma unroll
-    for (int g = 0; g < 8; ++g) {
-        const float4 a4 = ar[2 * g], b4 = br[2 * g];
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, b4.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b4.y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b4.z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, b4.w, acc, 0, 0, 0);
-    }
-}
-// acc += A . B : out[i][n] = sum_k A[i][k] B[k][n]   (A row-major b128; B read down its rows, lanes along n)
-__device__ __forceinline__ void mm_rows_cols(f32x16& acc, const float* A, const float* B, int i0, int n0, int j, int half) {
-    const float4* ar = reinterpret_cast<const float4*>(A + (i0 + j) * AS) + half;
-    const float* bc = B + n0 + j;
-#pragma unroll
-    for (int g = 0; g < 8; ++g) {
-        const float4 a4 = ar[2 * g];
-        const int k = 8 * g + 4 * half;
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, bc[(k + 0) * AS], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, bc[(k + 1) * AS], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, bc[(k + 2) * AS], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, bc[(k + 3) * AS], acc, 0, 0, 0);
-    }
-}
-// acc += A^T . B : out[m][n] = sum_k A[k][m] B[k][n]   (both read down their rows)
-__device__ __forceinline__ void mm_cols_cols(f32x16& acc, const float* A, const float* B, int m0, int n0, int j, int half) {
-    const float* ac = A + m0 + j;
-    const float* bc = B + n0 + j;
-#pragma unroll
-    for (int g = 0; g < 8; ++g) {
-        const int k = 8 * g + 4 * half;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[(k + c) * AS], bc[(k + c) * AS], acc, 0, 0, 0);
-    }
-}
-__device__ __forceinline__ void acc_zero(f32x16& a) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) a[r] = 0.f;
-}
-// scatter a wave's 32x32 accumulator block into an LDS [64][AS] matrix
-__device__ __forceinline__ void acc_to_lds(const f32x16& a, float* M, int i0, int j0, int j, int half, float scale) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) M[(i0 + (r & 3) + 8 * (r >> 2) + 4 * half) * AS + j0 + j] = a[r] * scale;
-}
-
-// NH heads' worth of [L x 64] blocks (column offsets col[0..NH-1]) of a [B*L, ld] matrix given as nsplit slabs (+ bias) -> LDS
-// [64][AS] images dst[0..NH-1], zero rows >= L.  Loop order: slab outermost, the thread's 4*NH float4s inside -- 4*NH
-// independent loads in flight per slab (a per-element slab loop would chain nsplit*4*NH load latencies: measured 18 us of the
-// 22 us the kernel took).
-template <int NH, int CH>
-__device__ __forceinline__ void load_heads(const float* src, int nsplit, int64_t slab, const float* bias, int64_t row0, int ld,
-                                           const int (&col)[NH], int L, float* const (&dst)[NH]) {
-    float4 v[NH][4];
-    const int d = (threadIdx.x & 15) * 4, t0 = threadIdx.x >> 4;  // rows t0, t0+16, t0+32, t0+48
-#pragma unroll
-    for (int a = 0; a < NH; ++a)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[a][q] = make_float4(0.f, 0.f, 0.f, 0.f);
-    // CH slabs per pass: all 4*NH*CH loads of a pass are issued before the first add (the slabs were written by the previous
-    // kernel on other XCDs: every load is an L2 miss of ~1-2 us, and a slab-at-a-time loop would pay that nsplit times)
-    for (int base = 0; base < nsplit; base += CH) {
-        float4 w[CH][NH][4];
-#pragma unroll
-        for (int c = 0; c < CH; ++c)
-#pragma unroll
-            for (int a = 0; a < NH; ++a)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int t = t0 + 16 * q;
-                    w[c][a][q] = (base + c < nsplit && t < L)
-                                     ? *reinterpret_cast<const float4*>(src + (base + c) * slab + (row0 + t) * ld + col[a] + d)
-                                     : make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-#pragma unroll
-        for (int c = 0; c < CH; ++c)
-#pragma unroll
-            for (int a = 0; a < NH; ++a)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) v[a][q] = add4(v[a][q], w[c][a][q]);
-    }
-#pragma unroll
-    for (int a = 0; a < NH; ++a) {
-        const float4 bv = bias ? *reinterpret_cast<const float4*>(bias + col[a] + d) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int t = t0 + 16 * q;
-            *reinterpret_cast<float4*>(dst[a] + t * AS + d) = t < L ? add4(v[a][q], bv) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    }
-}
 
 // Row-wise passes over a [64][AS] LDS matrix with FOUR ADJACENT LANES per row (thread = 4*row + quarter; quarter c owns
 // columns c, c+4, ..., c+60: conflict-free LDS access) so that the row reductions are two DPP quad permutes instead of six
 // ds_bpermute steps per reduction (one wave per row cost 5.6 us of shuffles per pass).
-__device__ __forceinline__ float quad_xor1(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, false));  // quad_perm [1,0,3,2]
-}
-__device__ __forceinline__ float quad_xor2(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, false));  // quad_perm [2,3,0,1]
-}
-__device__ __forceinline__ float quad_sum(float v) {
-    v += quad_xor1(v);
-    return v + quad_xor2(v);
-}
-__device__ __forceinline__ float quad_max(float v) {
-    v = fmaxf(v, quad_xor1(v));
-    return fmaxf(v, quad_xor2(v));
-}
-
 // P (logits) -> softmax over columns [0,L); rows >= L and columns >= L become 0.
 __device__ __forceinline__ void softmax_rows(float* P, int L) {
     const int i = threadIdx.x >> 2, c = threadIdx.x & 3;
@@ -342,26 +214,26 @@ __global__ __launch_bounds__(256) void attn2_fwd_kernel(const float* __restrict_
     {
         const int cols[3] = {h * 64, (H + h) * 64, (2 * H + h) * 64};
         float* const dsts[3] = {q, k, v};
-        load_heads<3, 3>(qkv, nsplit, slab, bias, (int64_t)b * L, ld, cols, L, dsts);
+        load_heads<3, 3, 16, AS>(qkv, nsplit, slab, bias, (int64_t)b * L, ld, cols, L, dsts);
     }
     __syncthreads();
     const int i0 = (wave >> 1) * 32, j0 = (wave & 1) * 32;
     f32x16 acc;
     acc_zero(acc);
-    mm_rows_rows(acc, q, k, i0, j0, j, half);
-    acc_to_lds(acc, p, i0, j0, j, half, 0.125f);
+    mm_rows_rows<AS, AS>(acc, q, k, i0, j0, j, half);
+    acc_to_lds<AS>(acc, p, i0, j0, j, half, 0.125f);
     __syncthreads();
     softmax_rows(p, L);
     __syncthreads();
     acc_zero(acc);
-    mm_rows_cols(acc, p, v, i0, j0, j, half);  // O[i][d] = sum_j P[i][j] V[j][d]
+    mm_rows_cols<AS, AS, 8>(acc, p, v, i0, j0, j, half);  // O[i][d] = sum_j P[i][j] V[j][d]
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int i = i0 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        const int i = i0 + acc_row(r, half);
         if (i >= L) continue;
         const int64_t m = (int64_t)b * L + i;
         const int n = h * 64 + j0 + j;
-        if (out_mpad > 0) out[((int64_t)(n >> 2) * out_mpad + m) * 4 + (n & 3)] = acc[r];  // K-quad-major (vit3.hip): the out-projection's A operand
+        if (out_mpad > 0) out[kq_index(m, n, out_mpad)] = acc[r];  // K-quad-major: the out-projection's A operand
         else out[m * (H * 64) + n] = acc[r];
     }
 }
@@ -382,19 +254,19 @@ __global__ __launch_bounds__(256) void attn2_bwd_kernel(const float* __restrict_
     {
         const int cols[3] = {h * 64, (H + h) * 64, (2 * H + h) * 64};
         float* const dsts[3] = {q, k, v};
-        load_heads<3, 3>(qkv, nsplit, slab, bias, (int64_t)b * L, ld, cols, L, dsts);
+        load_heads<3, 3, 16, AS>(qkv, nsplit, slab, bias, (int64_t)b * L, ld, cols, L, dsts);
         const int gcol[1] = {h * 64};
         float* const gdst[1] = {go};
-        load_heads<1, 6>(gout, gsplit, gslab, nullptr, (int64_t)b * L, H * 64, gcol, L, gdst);
+        load_heads<1, 6, 16, AS>(gout, gsplit, gslab, nullptr, (int64_t)b * L, H * 64, gcol, L, gdst);
     }
     __syncthreads();
     const int i0 = (wave >> 1) * 32, j0 = (wave & 1) * 32;
     f32x16 acc, acc2;
     acc_zero(acc), acc_zero(acc2);
-    mm_rows_rows(acc, q, k, i0, j0, j, half);    // S
-    mm_rows_rows(acc2, go, v, i0, j0, j, half);  // dP[i][j] = dO_i . V_j
-    acc_to_lds(acc, p, i0, j0, j, half, 0.125f);
-    acc_to_lds(acc2, ds, i0, j0, j, half, 1.f);
+    mm_rows_rows<AS, AS>(acc, q, k, i0, j0, j, half);    // S
+    mm_rows_rows<AS, AS>(acc2, go, v, i0, j0, j, half);  // dP[i][j] = dO_i . V_j
+    acc_to_lds<AS>(acc, p, i0, j0, j, half, 0.125f);
+    acc_to_lds<AS>(acc2, ds, i0, j0, j, half, 1.f);
     __syncthreads();
     softmax_rows(p, L);
     __syncthreads();  // (a row's four lanes wrote each other's columns)
@@ -402,17 +274,17 @@ __global__ __launch_bounds__(256) void attn2_bwd_kernel(const float* __restrict_
     __syncthreads();
     f32x16 gq, gk, gv;
     acc_zero(gq), acc_zero(gk), acc_zero(gv);
-    mm_rows_cols(gq, ds, k, i0, j0, j, half);   // dQ[i][d] = sum_j dS[i][j] K[j][d]
-    mm_cols_cols(gk, ds, q, i0, j0, j, half);   // dK[j][d] = sum_i dS[i][j] Q[i][d]
-    mm_cols_cols(gv, p, go, i0, j0, j, half);   // dV[j][d] = sum_i P[i][j] dO[i][d]
+    mm_rows_cols<AS, AS, 8>(gq, ds, k, i0, j0, j, half);  // dQ[i][d] = sum_j dS[i][j] K[j][d]
+    mm_cols_cols<AS, AS>(gk, ds, q, i0, j0, j, half);     // dK[j][d] = sum_i dS[i][j] Q[i][d]
+    mm_cols_cols<AS, AS>(gv, p, go, i0, j0, j, half);     // dV[j][d] = sum_i P[i][j] dO[i][d]
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int t = i0 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        const int t = i0 + acc_row(r, half);
         if (t >= L) continue;
         if (g_mpad > 0) {  // K-quad-major (vit3.hip): the A operand of the in-projection's input-gradient GEMM
             const int64_t m = (int64_t)b * L + t;
             const int n = h * 64 + j0 + j;
-            float* dst = gqkv + ((int64_t)(n >> 2) * g_mpad + m) * 4 + (n & 3);
+            float* dst = gqkv + kq_index(m, n, g_mpad);
             const int64_t third = (int64_t)(H * 64 / 4) * g_mpad * 4;  // H*64 columns further = H*16 quads further
             dst[0] = gq[r] * 0.125f;
             dst[third] = gk[r] * 0.125f;

@@ -90,12 +90,7 @@ class _LayerNorm(torch.autograd.Function):
     def forward(ctx, x, weight, bias, eps):
         _frozen(weight, bias)
         x2 = _c(x).reshape(-1, x.shape[-1])
-        rows, dim = x2.shape
-        y = torch.empty_like(x2)
-        mean = torch.empty(rows, device=x.device, dtype=torch.float32)
-        rstd = torch.empty(rows, device=x.device, dtype=torch.float32)
-        call("w2e_layernorm_fwd", ptr(x2), ptr(_c(weight)), ptr(_c(bias)), ptr(y), ptr(mean), ptr(rstd), rows, dim,
-             float(eps), stream_ptr())
+        y, mean, rstd = _ln_fwd(x2, _c(weight), _c(bias), eps)
         ctx.save_for_backward(x2, weight, mean, rstd)
         ctx.shape = x.shape
         return y.reshape(x.shape)
@@ -328,6 +323,32 @@ def _gemm_pk(a_packed, m, mpad, wpk):
     return c
 
 
+def _block_fwd(blk, params, pend, pbias, pres, geom, wpk, attn_entry):
+    """The forward of one residual block on the M = batch*seq kernels, entered with the previous block's c_proj output still pending as
+    split-K slabs (`pend` [S, M, D] + `pbias` + `pres`): reduce+LN, QKV GEMM, attention (`attn_entry`: "w2e_attn2_fwd" for the visual
+    tower, "w2e_attn_causal_fwd" for the text tower), out-proj GEMM, reduce+LN, c_fc GEMM, reduce + QuickGELU pair, c_proj GEMM.
+    `params`: _block_params(blk) -- the PARAMETERS themselves (wpk's cache is keyed on their id).  Returns the new pending triple and the
+    tensors the backward needs."""
+    b, l, dim, heads = geom
+    m = b * l
+    mpad = _pad(m, 32)
+    dev = pend.device
+    ln1_w, ln1_b, in_w, in_b, out_w, out_b, ln2_w, ln2_b, fc_w, fc_b, proj_w, proj_b = params
+    xr, y1, mean1, rstd1 = _reduce_ln(pend, pbias, pres, ln1_w, ln1_b, blk.ln_1.eps, mpad=mpad)
+    qkv = _gemm_pk(y1, m, mpad, wpk.fwd(in_w))
+    att = torch.empty((dim // 4, mpad, 4), device=dev, dtype=torch.float32)
+    call(attn_entry, ptr(qkv), qkv.shape[0], m * 3 * dim, ptr(in_b), ptr(att), b, l, heads, mpad, stream_ptr())
+    o = _gemm_pk(att, m, mpad, wpk.fwd(out_w))
+    x_mid, y2, mean2, rstd2 = _reduce_ln(o, out_b, xr, ln2_w, ln2_b, blk.ln_2.eps, mpad=mpad)
+    hp = _gemm_pk(y2, m, mpad, wpk.fwd(fc_w))
+    n_fc = fc_w.shape[0]
+    h = torch.empty((m, n_fc), device=dev, dtype=torch.float32)
+    g = torch.empty((n_fc // 4, mpad, 4), device=dev, dtype=torch.float32)
+    call("w2e_reduce_gelu", ptr(hp), hp.shape[0], m * n_fc, ptr(fc_b), None, ptr(h), ptr(g), m, n_fc, 0, mpad, stream_ptr())
+    pend = _gemm_pk(g, m, mpad, wpk.fwd(proj_w))
+    return (pend, proj_b, x_mid), (xr, mean1, rstd1, qkv, x_mid, mean2, rstd2, h)
+
+
 class _TransformerV3(torch.autograd.Function):
     """All residual blocks of the visual tower as ONE autograd node on the M = 50*batch kernels: per block 7 launches forward (reduce+LN,
     QKV GEMM, attention, out-proj GEMM, reduce+LN, c_fc GEMM, reduce + QuickGELU pair -- then c_proj's GEMM opens the next block's
@@ -339,29 +360,14 @@ class _TransformerV3(torch.autograd.Function):
     def forward(ctx, x, heads, wpk, blocks):
         b, l, dim = x.shape
         m = b * l
-        mpad = _pad(m, 32)
         x2 = _c(x).reshape(m, dim)
         saved = []
         pend, pbias, pres = x2.view(1, m, dim), None, None
-        dev = x.device
         for blk in blocks:
             p = _block_params(blk)
             _frozen(*p)
-            ln1_w, ln1_b, in_w, in_b, out_w, out_b, ln2_w, ln2_b, fc_w, fc_b, proj_w, proj_b = p
-            xr, y1, mean1, rstd1 = _reduce_ln(pend, pbias, pres, ln1_w, ln1_b, blk.ln_1.eps, mpad=mpad)
-            qkv = _gemm_pk(y1, m, mpad, wpk.fwd(in_w))
-            att = torch.empty((dim // 4, mpad, 4), device=dev, dtype=torch.float32)
-            call("w2e_attn2_fwd", ptr(qkv), qkv.shape[0], m * 3 * dim, ptr(in_b), ptr(att), b, l, heads, mpad, stream_ptr())
-            o = _gemm_pk(att, m, mpad, wpk.fwd(out_w))
-            x_mid, y2, mean2, rstd2 = _reduce_ln(o, out_b, xr, ln2_w, ln2_b, blk.ln_2.eps, mpad=mpad)
-            hp = _gemm_pk(y2, m, mpad, wpk.fwd(fc_w))
-            n_fc = fc_w.shape[0]
-            h = torch.empty((m, n_fc), device=dev, dtype=torch.float32)
-            g = torch.empty((n_fc // 4, mpad, 4), device=dev, dtype=torch.float32)
-            call("w2e_reduce_gelu", ptr(hp), hp.shape[0], m * n_fc, ptr(fc_b), None, ptr(h), ptr(g), m, n_fc, 0, mpad, stream_ptr())
-            pend = _gemm_pk(g, m, mpad, wpk.fwd(proj_w))
-            pbias, pres = proj_b, x_mid
-            saved.append((xr, mean1, rstd1, qkv, x_mid, mean2, rstd2, h))
+            (pend, pbias, pres), blk_saved = _block_fwd(blk, p, pend, pbias, pres, (b, l, dim, heads), wpk, "w2e_attn2_fwd")
+            saved.append(blk_saved)
         out, _, _, _ = _reduce_ln(pend, pbias, pres, None, None, 0.0, want_y=False)
         ctx.save_for_backward(*[t for blk_saved in saved for t in blk_saved])
         ctx.blocks, ctx.wpk, ctx.geom = blocks, wpk, (b, l, dim, heads)
@@ -453,7 +459,7 @@ def text_hip_ok(clip, tokens):
 
 
 def text_forward(clip, tokens):
-    """CLIP.encode_text on the block kernels: embed -> per block the visual tower's forward (_TransformerV3) with the causal attention
+    """CLIP.encode_text on the block kernels: embed -> per block the visual tower's forward (_block_fwd) with the causal attention
     kernel in place of attn2 -> EOT pooling + ln_final -> text_projection.  Forward only (no autograd node: the input is integer tokens
     and the tower is frozen); the packed weights are cached per parameter version in clip._text_wpk."""
     b, l = tokens.shape
@@ -469,27 +475,13 @@ def text_forward(clip, tokens):
         clip._text_wpk = _WeightsPk(False)
     wpk = clip._text_wpk
     m = b * l
-    mpad = _pad(m, 32)
     with torch.no_grad():
         x = torch.empty((m, dim), device=dev, dtype=torch.float32)
         call("w2e_text_embed", ctypes.c_void_p(tok.data_ptr()), tbytes, ptr(_c(emb.detach())), emb.shape[0],
              ptr(_c(clip.positional_embedding.detach())), ptr(x), b, l, dim, stream_ptr())
         pend, pbias, pres = x.view(1, m, dim), None, None
         for blk in clip.transformer.resblocks:
-            ln1_w, ln1_b, in_w, in_b, out_w, out_b, ln2_w, ln2_b, fc_w, fc_b, proj_w, proj_b = (t.detach() for t in _block_params(blk))
-            xr, y1, _, _ = _reduce_ln(pend, pbias, pres, ln1_w, ln1_b, blk.ln_1.eps, mpad=mpad)
-            qkv = _gemm_pk(y1, m, mpad, wpk.fwd(blk.attn.in_proj_weight))
-            att = torch.empty((dim // 4, mpad, 4), device=dev, dtype=torch.float32)
-            call("w2e_attn_causal_fwd", ptr(qkv), qkv.shape[0], m * 3 * dim, ptr(in_b), ptr(att), b, l, heads, mpad, stream_ptr())
-            o = _gemm_pk(att, m, mpad, wpk.fwd(blk.attn.out_proj.weight))
-            x_mid, y2, _, _ = _reduce_ln(o, out_b, xr, ln2_w, ln2_b, blk.ln_2.eps, mpad=mpad)
-            hp = _gemm_pk(y2, m, mpad, wpk.fwd(blk.mlp.c_fc.weight))
-            n_fc = fc_w.shape[0]
-            h = torch.empty((m, n_fc), device=dev, dtype=torch.float32)
-            g = torch.empty((n_fc // 4, mpad, 4), device=dev, dtype=torch.float32)
-            call("w2e_reduce_gelu", ptr(hp), hp.shape[0], m * n_fc, ptr(fc_b), None, ptr(h), ptr(g), m, n_fc, 0, mpad, stream_ptr())
-            pend = _gemm_pk(g, m, mpad, wpk.fwd(blk.mlp.c_proj.weight))
-            pbias, pres = proj_b, x_mid
+            (pend, pbias, pres), _ = _block_fwd(blk, _block_params(blk), pend, pbias, pres, (b, l, dim, heads), wpk, "w2e_attn_causal_fwd")
         pooled = torch.empty((b, dim), device=dev, dtype=torch.float32)
         call("w2e_text_pool", ptr(pend), pend.shape[0], m * dim, ptr(pbias), ptr(pres), ctypes.c_void_p(tok.data_ptr()), tbytes, b, l,
              ptr(clip.ln_final.weight.detach()), ptr(clip.ln_final.bias.detach()), float(clip.ln_final.eps), ptr(pooled), dim, stream_ptr())
