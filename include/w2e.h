@@ -39,7 +39,8 @@ extern "C" {
 /* 6: additive over 5 -- w2e_maxpool2x2_fwd / w2e_maxpool2x2_relu_bwd / w2e_mse_relu_fwd (w2e_irse.h, the VGG16 perceptual loss) */
 /* 7: additive over 6 -- w2e_modconv_wgrad_plan / w2e_modconv_wgrad / w2e_modconv_wgrad_finish / w2e_modconv_wsq (K1d, the conv-weight
  * gradient of decoder fine-tuning).  Still 7 after these additions, no existing signature or mode changed: the K1d modes 3 (DOWN) and
- * 4 (DOWN-CENTRE), and K8 (w2e_fromrgb_fwd / w2e_fromrgb_bwd_rows / w2e_fromrgb_bwd / w2e_mbstd_fwd / w2e_mbstd_bwd, the Discriminator) */
+ * 4 (DOWN-CENTRE), K8 (w2e_fromrgb_fwd / w2e_fromrgb_bwd_rows / w2e_fromrgb_bwd / w2e_mbstd_fwd / w2e_mbstd_bwd, the Discriminator), and
+ * K8's forward-mode entries for the R1 penalty (w2e_fromrgb_jvp / w2e_mbstd_jvp / w2e_mbstd_hvp / w2e_sumsq_rows_parts / w2e_sumsq_rows) */
 #define W2E_VERSION 7
 
 int w2e_version(void);
@@ -247,6 +248,20 @@ int w2e_fromrgb_bwd(const float* gy, const float* y, const float* x, const float
                     int batch, int channels, int64_t hw, float scale, void* stream);
 int w2e_mbstd_fwd(const float* x, float* y, int batch, int channels, int hw, void* stream);
 int w2e_mbstd_bwd(const float* gy, const float* x, float* gx, int batch, int channels, int hw, void* stream);
+/* The forward-mode halves the R1 gradient penalty needs ("R1"):
+ * w2e_fromrgb_jvp: the tangent of w2e_fromrgb_fwd along dx [B,3,hw], from the saved output y (no bias; the slope as a mask):
+ *   t[b,o,p] = sqrt2 * (y[b,o,p] > 0 ? 1 : 0.2) * scale * sum_i weight[o,i] dx[b,i,p]
+ * w2e_mbstd_jvp: the tangent of w2e_mbstd_fwd along dx [B,C,hw], same [B,C+1,hw] layout: y[b,:C] = dx[b]; y[b,C,:] = d stddev.
+ * w2e_mbstd_hvp: mu [B,C,hw] = d/dx of <gy[:, C], d stddev(x, dx)> (gy [B,C+1,hw], only its stddev channel is read): the one
+ *   second-order term of the Discriminator (every other layer is piecewise linear).
+ * w2e_sumsq_rows: out[b] = sum_j x[b,j]^2 of x [B,n] in two stages of fixed order; part: workspace of
+ *   B * w2e_sumsq_rows_parts(n) floats (0 = n out of range). */
+int w2e_fromrgb_jvp(const float* dx, const float* y, const float* weight, float* t, int batch, int channels, int64_t hw, float scale,
+                    void* stream);
+int w2e_mbstd_jvp(const float* x, const float* dx, float* y, int batch, int channels, int hw, void* stream);
+int w2e_mbstd_hvp(const float* gy, const float* x, const float* dx, float* mu, int batch, int channels, int hw, void* stream);
+int w2e_sumsq_rows_parts(int64_t n);
+int w2e_sumsq_rows(const float* x, float* part, float* out, int batch, int64_t n, void* stream);
 
 /* All style modulations of one generator pass in one launch (model.py:211, `style = self.modulation(style)` in each of
  * the 26 ModulatedConv2d): every layer's EqualLinear(style_dim, cin_l) -- weight*scale and bias*lr_mul, model.py:151-158

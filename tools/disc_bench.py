@@ -3,8 +3,11 @@ composition of the reference's arithmetic (tests/disc64.py's restatement in fp32
 Three variants each: forward; forward + input gradient with a frozen D (the generator step); forward + every gradient (the D step).
 Device-event timing around single calls after a warm-up; the median of --iters calls, with TFLOP/s against the arithmetic of the
 convolutions (~150 GFLOP per image forward, the backward twice that with weight gradients, once without).
+The variant `r1` (not in the default list; batch 4 and 8 are the ones of interest) times one `d.r1_penalty(x).backward()` (four passes over D)
+next to the D step of the same run and next to the stock-op composition: stock D, autograd.grad(create_graph=True), backward.
 
     python tools/disc_bench.py [--batches 1,4,8] [--iters 10] [--out FILE.jsonl]
+    python tools/disc_bench.py --batches 4,8 --variants dstep,r1 --out profiles/r1_bench.jsonl
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/disc_bench.py --hip-only --batches 4 --variants dstep --iters 5"""
 import argparse
 import json
@@ -70,14 +73,18 @@ def main():
     for b in [int(v) for v in a.batches.split(",")]:
         x = disc64.images(b, SIZE).cuda()
         for var in a.variants.split(","):
-            mult = {"fwd": 1.0, "gstep": 2.0, "dstep": 3.0}[var]
+            # r1: forward, reverse, tangent forward + its weight gradients (two forwards' worth), plus the small fourth pass
+            mult = {"fwd": 1.0, "gstep": 2.0, "dstep": 3.0, "r1": 5.0}[var]
 
             def hip():
                 if var == "fwd":
                     with torch.no_grad():
                         d(x)
                     return
-                d.requires_grad_(var == "dstep")
+                d.requires_grad_(var in ("dstep", "r1"))
+                if var == "r1":
+                    torch.autograd.grad(d.r1_penalty(x), [p for k, p in d.named_parameters() if k != "final_linear.1.bias"])
+                    return
                 xx = x.requires_grad_(var == "gstep")
                 loss = d(xx).sum()
                 if var == "gstep":
@@ -90,7 +97,12 @@ def main():
                     with torch.no_grad():
                         disc64.forward(sdc, x)
                     return
-                if var == "gstep":
+                if var == "r1":
+                    xx = x.clone().requires_grad_(True)
+                    (g,) = torch.autograd.grad(disc64.forward(params_stock, xx).sum(), [xx], create_graph=True)
+                    ps = [v for k, v in params_stock.items() if not k.endswith(".kernel") and k != "final_linear.1.bias"]
+                    torch.autograd.grad(g.pow(2).reshape(b, -1).sum(1).mean(), ps, allow_unused=True)
+                elif var == "gstep":
                     xx = x.clone().requires_grad_(True)
                     torch.autograd.grad(disc64.forward(sdc, xx).sum(), [xx])
                 else:
@@ -104,10 +116,10 @@ def main():
                 rec["stock_tflops"] = round(mult * fl * b / rec["stock_ms"] / 1e9, 1)
             print(json.dumps(rec), flush=True)
             lines.append(rec)
-    if a.out:
-        with open(a.out, "w") as f:
-            for r in lines:
-                f.write(json.dumps(r) + "\n")
+            if a.out:  # rewritten after every record: a run that is cut short leaves the lines it measured
+                with open(a.out, "w") as f:
+                    for r in lines:
+                        f.write(json.dumps(r) + "\n")
 
 
 if __name__ == "__main__":

@@ -42,3 +42,10 @@ def train_mask_branch(net, enabled=True):
     (or enabled=False) undoes it."""
     from .run_attention import train_mask_branch as _train
     return _train(net, enabled)
+
+
+def r1_penalty(discriminator, real, return_logits=False):
+    """The R1 gradient penalty of a stylegan2.Discriminator on `real` (disc_hip.r1_penalty): one HIP autograd node over the
+    Discriminator's parameters; `(r1_gamma / 2 * r1_penalty(d, real) * d_reg_every).backward()` is the lazy-regularisation step."""
+    from .disc_hip import r1_penalty as _r1
+    return _r1(discriminator, real, return_logits)

@@ -55,6 +55,11 @@ _PROTOS = {
     "w2e_fromrgb_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _F, _P]),
     "w2e_mbstd_fwd": (_I, [_P, _P, _I, _I, _I, _P]),
     "w2e_mbstd_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "w2e_fromrgb_jvp": (_I, [_P, _P, _P, _P, _I, _I, _L, _F, _P]),
+    "w2e_mbstd_jvp": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "w2e_mbstd_hvp": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "w2e_sumsq_rows_parts": (_I, [_L]),
+    "w2e_sumsq_rows": (_I, [_P, _P, _P, _I, _L, _P]),
     "w2e_style_affine_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "w2e_style_affine_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "w2e_torgb_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),

@@ -689,8 +689,9 @@ class ResBlock(nn.Module):
 class Discriminator(nn.Module):
     """model.py:650-705.  Same constructor, module tree, state_dict keys and [B,1] logits as the reference; forward and backward on
     the HIP kernels (disc_hip).  A Discriminator is trainable by default: the parameters that require grad get gradients from the
-    kernels (freeze it with requires_grad_(False) for the generator step: then no weight-gradient kernel runs).  Double backward
-    (R1's create_graph=True) raises: the kernels' autograd nodes are once_differentiable.  The minibatch-stddev layer needs
+    kernels (freeze it with requires_grad_(False) for the generator step: then no weight-gradient kernel runs).  The R1 gradient
+    penalty of the D regularisation step is r1_penalty (one HIP autograd node over the parameters); generic double backward
+    (create_graph=True) still raises: the kernels' autograd nodes are once_differentiable.  The minibatch-stddev layer needs
     B % min(B, 4) == 0 (ValueError otherwise; the reference's view() fails there)."""
 
     def __init__(self, size, channel_multiplier=2, blur_kernel=[1, 3, 3, 1]):
@@ -724,3 +725,10 @@ class Discriminator(nn.Module):
         out = self.final_conv(out)
         out = out.view(batch, -1)
         return self.final_linear(out)
+
+    def r1_penalty(self, real, return_logits=False):
+        """mean_b |d sum(D(real)) / d real_b|^2 (rosinality's d_r1_loss) through disc_hip.r1_penalty: differentiable with respect to
+        the parameters, not to `real` (whose requires_grad is accepted and ignored).  Lazy regularisation:
+        `(r1_gamma / 2 * d.r1_penalty(real) * d_reg_every).backward()`."""
+        from . import disc_hip
+        return disc_hip.r1_penalty(self, real, return_logits)
