@@ -40,7 +40,8 @@ extern "C" {
 /* 7: additive over 6 -- w2e_modconv_wgrad_plan / w2e_modconv_wgrad / w2e_modconv_wgrad_finish / w2e_modconv_wsq (K1d, the conv-weight
  * gradient of decoder fine-tuning).  Still 7 after these additions, no existing signature or mode changed: the K1d modes 3 (DOWN) and
  * 4 (DOWN-CENTRE), K8 (w2e_fromrgb_fwd / w2e_fromrgb_bwd_rows / w2e_fromrgb_bwd / w2e_mbstd_fwd / w2e_mbstd_bwd, the Discriminator), and
- * K8's forward-mode entries for the R1 penalty (w2e_fromrgb_jvp / w2e_mbstd_jvp / w2e_mbstd_hvp / w2e_sumsq_rows_parts / w2e_sumsq_rows) */
+ * K8's forward-mode entries for the R1 penalty (w2e_fromrgb_jvp / w2e_mbstd_jvp / w2e_mbstd_hvp / w2e_sumsq_rows_parts / w2e_sumsq_rows), and
+ * w2e_mask_iou_counts (w2e_attention.h, the mask IoU evaluation) */
 #define W2E_VERSION 7
 
 int w2e_version(void);

@@ -145,6 +145,18 @@ int w2e_cluster_pool_bwd(const float* g_final, const float* each, const float* s
                          const int32_t* assign, const float* g_loss_reg, const float* g_loss_tv, float* g_each, int batch,
                          int size, int csize, int clusters, void* stream);
 
+/* ---- evaluation: the confusion counts of the mask IoU against parsing labels (utils.py:654-726; csrc/evaluate.hip) ----
+ * mask [B,T,S,S] fp32, one soft or binary mask per prompt / region t; label [B,S,S] raw parsing ids; lut [256] raw id -> region in
+ * 0..T (0 = none; the caller builds and validates it: an entry above T matches no region here); counts [T,3] 64-bit.
+ * With pred = mask >= threshold (compared in fp32; a NaN is not predicted) and real = (lut[label] == t + 1):
+ *   counts[t,0] += #(pred and real)    counts[t,1] += #pred    counts[t,2] += #real
+ * ACCUMULATED, so that a caller streams batches into one table it zeroed once.  1 <= T <= 16, any S >= 1, B*S*S <= 2^40 per call.
+ * 16-byte mask loads where S*S % 4 == 0, mask is 16-byte and label 4-byte aligned; one pixel per thread otherwise.  One 64-bit
+ * integer atomic add per workgroup and counter (integer: bit-identical from run to run, also with "deterministic" = 1, which
+ * forbids fp32 atomics); no memsets, no host synchronisation. */
+int w2e_mask_iou_counts(const float* mask, const uint8_t* label, const uint8_t* lut, float threshold, int batch, int classes,
+                        int size, unsigned long long* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@ Layout:
   perceptual_loss.py                       criteria/perceptual_loss.py surface: VGG16 relu2_2 MSE on the conv engine
   coach.py, ranger.py     the mapper training step (mapper/training/coach.py:70-92) + optimizer
   dist.py                 data-parallel step: shard latents, one RCCL all-reduce of mapper grads
+  evaluation.py           the region mask's IoU against parsing labels (utils.py:639-726): MaskIoU, calculate_iou
 """
 __version__ = "0.1.0"
 
@@ -49,3 +50,14 @@ def r1_penalty(discriminator, real, return_logits=False):
     Discriminator's parameters; `(r1_gamma / 2 * r1_penalty(d, real) * d_reg_every).backward()` is the lazy-regularisation step."""
     from .disc_hip import r1_penalty as _r1
     return _r1(discriminator, real, return_logits)
+
+
+# where2edit_amd.evaluation's public names, importable from the package (resolved on first use: importing the package stays light)
+_EVALUATION = ("CELEBAMASK_REGIONS", "region_lut", "binarise", "attention_with_text", "MaskIoU", "calculate_iou")
+
+
+def __getattr__(name):
+    if name in _EVALUATION:
+        from . import evaluation
+        return getattr(evaluation, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

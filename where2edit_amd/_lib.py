@@ -74,6 +74,7 @@ _PROTOS = {
     "w2e_id_preproc_bwd": (_I, [_P, _P, _L, _I, _P]),
     "w2e_mask_blend_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "w2e_mask_blend_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "w2e_mask_iou_counts": (_I, [_P, _P, _P, _F, _I, _I, _I, _P, _P]),  # include/w2e_attention.h (evaluation.py)
 }
 
 _lib = None

@@ -414,6 +414,14 @@ class FullSpaceMapperFEATClusterLinStyle_Net(nn.Module):
         del keep
         return each, assign
 
+    @torch.no_grad()
+    def mask(self, feature_map, size, attention_text, n_codes):
+        """The mask branch alone: what `forward` returns as its second output ([B,1,size,size], thresholded and blurred), without the
+        style branch -- for callers that want the mask of a prompt and nothing else (evaluation.calculate_iou; the reference runs the
+        whole net per prompt and drops the styles, utils.py:639-651).  `n_codes`: the number of S-space codes `forward` would get."""
+        each, assign = self.attention_map(feature_map, size, attention_text.detach().float(), n_codes)
+        return cluster_pool(each, assign, size, self.clusters)[4]
+
     def attention_map_train(self, feature_map, size, attention_text, n_codes, noises=None):
         """attention_map with gradients (train_mask_branch): the same kernels inside _MaskLogitsTrain.  The style EqualLinears and the
         [C,32] scaled weights are stock ops on the live parameters (differentiable; no version-keyed cache on this path); the noise of
