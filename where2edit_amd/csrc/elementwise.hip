@@ -516,15 +516,16 @@ int w2e_mask_blend_bwd(const float* gout, const float* a, const float* b, const 
     W2E_REQUIRE(batch >= 0 && channels > 0 && h > 0 && w > 0 && ms > 0, "mask_blend_bwd: bad dims");
     if (batch == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
+    // gmask: one atomic per pixel into its mask cell.  With the mask at the layer's resolution (the shipped setting:
+    // attention_layer 13 = 64x64 features, 64x64 mask) every cell receives exactly ONE add: order-free.  Otherwise the
+    // adds of a cell's pixels race; the deterministic mode refuses that geometry instead of giving run-to-run noise.
+    // Refused before the memset, so that a refused call has written nothing.
+    W2E_REQUIRE(!(options().deterministic && gmask && (h != ms || w != ms)),
+                "mask_blend_bwd: deterministic mode needs the mask at the feature resolution (%dx%d vs %d)", h, w, ms);
     if (gmask && zero_async(gmask, sizeof(float) * (size_t)batch * ms * ms, s) != hipSuccess) {
         set_error("mask_blend_bwd: memset failed");
         return 2;
     }
-    // gmask: one atomic per pixel into its mask cell.  With the mask at the layer's resolution (the shipped setting:
-    // attention_layer 13 = 64x64 features, 64x64 mask) every cell receives exactly ONE add: order-free.  Otherwise the
-    // adds of a cell's pixels race; the deterministic mode refuses that geometry instead of giving run-to-run noise.
-    W2E_REQUIRE(!(options().deterministic && gmask && (h != ms || w != ms)),
-                "mask_blend_bwd: deterministic mode needs the mask at the feature resolution (%dx%d vs %d)", h, w, ms);
     const int threads = w >= 256 ? 256 : (w >= 128 ? 128 : 64);
     mask_blend_bwd_kernel<<<batch * h, threads, 0, s>>>(gout, a, b, mask, ga, gb, gmask, channels, h, w, ms);
     W2E_LAUNCH_CHECK("mask_blend_bwd");
