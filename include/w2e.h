@@ -41,7 +41,8 @@ extern "C" {
  * gradient of decoder fine-tuning).  Still 7 after these additions, no existing signature or mode changed: the K1d modes 3 (DOWN) and
  * 4 (DOWN-CENTRE), K8 (w2e_fromrgb_fwd / w2e_fromrgb_bwd_rows / w2e_fromrgb_bwd / w2e_mbstd_fwd / w2e_mbstd_bwd, the Discriminator), and
  * K8's forward-mode entries for the R1 penalty (w2e_fromrgb_jvp / w2e_mbstd_jvp / w2e_mbstd_hvp / w2e_sumsq_rows_parts / w2e_sumsq_rows), and
- * w2e_mask_iou_counts (w2e_attention.h, the mask IoU evaluation) */
+ * w2e_mask_iou_counts (w2e_attention.h, the mask IoU evaluation).
+ * Still 7: w2e_modconv_upblur / w2e_modconv_upblur_plan and the option tune_upblur are additive too */
 #define W2E_VERSION 7
 
 int w2e_version(void);
@@ -54,13 +55,13 @@ const char* w2e_last_error(void);
  *                                          cudnn.deterministic=True (attention/run_attention.py:903-904)
  *   "tune_cfg" [W2E_TUNE_CFG] "<cfg>[,<splits>[,<mode>]]" force a conv tile (tests, tools/layer_bench.py); "" = off.  A forced
  *   tile passes the selection's own feasibility filters (LDS, patch slots): one that does not fit a launch fails it
- *   "tune_upall", "tune_dma", "tune_fuse", "tune_print", "tune_blur", "tune_gemm_s": kernel-selection aids -- they
+ *   "tune_upall", "tune_dma", "tune_fuse", "tune_upblur", "tune_print", "tune_blur", "tune_gemm_s": kernel-selection aids -- they
  *   choose between kernels / tiles that compute the same result ("tune_blur": only bit 8, keep the LDS-tile FIR kernels
  *   for wide images; its bits 1/2/4 and "tune_skip" / "tune_clock" drop loads, arithmetic or stores, or synchronise,
  *   and are compiled in ONLY by -DW2E_TUNING: the shipped library ignores them)
  *   "debug_poison" [W2E_DEBUG_POISON] "1": host-side aid -- gradient rows the merged forward declares unused are
  *   filled with NaN instead of being left unwritten, so that a consumer that reads them fails loudly (tests)
- * w2e_get_option reads "conv_precision", "deterministic", "tune_cfg", "tuning_build" (1 = compiled with -DW2E_TUNING). */
+ * w2e_get_option reads "conv_precision", "deterministic", "tune_cfg", "tune_upblur", "tuning_build" (1 = compiled with -DW2E_TUNING). */
 int w2e_set_option(const char* name, const char* value);
 
 /* Row pitch (floats) of the phase planes of the transposed-conv output T for an input W wide: W+1 columns rounded up to 16 floats =
@@ -142,6 +143,21 @@ int w2e_conv_pack(const float* weight, float* wp, int cout, int cin, float scale
 int w2e_modconv3x3(int mode, const float* x, const float* wp, const float* in_scale, const float* out_scale,
                    float* y, int batch, int k_ch, int n_ch, int h, int w, int y_pitch, int act, const float* noise,
                    const float* noise_w, const float* bias, const float* dot_with, float* dot_out, void* stream);
+
+/* ---- K1u  the up-sampling StyledConv in ONE launch: W2E_CONV_UP with the 4x4 blur and the activation in the tile's epilogue -------
+ *     y[b,o] = lrelu(blur(out_scale[b,o] * conv_transpose(Wp, in_scale[b,i] * x[b,i])) + noise_w[0]*noise + bias[o], 0.2) * sqrt(2)
+ * -- what w2e_modconv3x3(W2E_CONV_UP) followed by w2e_upfirdn2d(4x4, pad 1, flip = 1, in_layout = 1, act = 1, out_scale = NULL,
+ * slope 0.2, gain sqrt 2) computes, to the summation order of the FIR; the (2H+1)x(2W+1) intermediate is never written.  kern: the
+ * [4,4] FIR taps on the device, as w2e_upfirdn2d takes them.  y: [B,N,2H,2W] (plain rows).  noise [2H*2W] / noise_w / bias [N] may be
+ * NULL.  Tiles of 16 x 32 input positions overlap by the blur's halo (14 x 30 owned: 1.3x the MFMA work at 512^2, more below), so
+ * the form pays only where the blur launch is dear: w2e_modconv_upblur_plan says (host code, no GPU) whether the library would
+ * use it for a shape -- option "tune_upblur" [W2E_TUNE_UPBLUR]: -1 (default) the layers it measured faster on, 0 never, 1 wherever
+ * it can run.  fp32 only: with conv_precision = bf16x3, or a split-K forced through tune_cfg, the plan says 0 and the launch is
+ * refused.  No allocation, no synchronisation: capture-safe. */
+int w2e_modconv_upblur_plan(int batch, int k_ch, int n_ch, int h, int w, int* fused);
+int w2e_modconv_upblur(const float* x, const float* wp, const float* in_scale, const float* out_scale, const float* kern,
+                       float* y, int batch, int k_ch, int n_ch, int h, int w, const float* noise, const float* noise_w,
+                       const float* bias, void* stream);
 
 /* ---- K1w  the FUSED Winograd F(4x4,3x3) form of W2E_CONV_SAME  (model.py:270-274; the same contract as w2e_modconv3x3) -------------
  *     y[b,o] = epilogue(out_scale[b,o] * A^T [ sum_i U[.,o,i] (.) V[.,i,t] ] A)

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Per-layer microbenchmark of the modulated-conv kernels at the FFHQ-1024 generator's layer shapes
-(HIP events on the launch stream, random data).  python tools/layer_bench.py [--batch 4]"""
+(HIP events on the launch stream, random data).  python tools/layer_bench.py [--batch 4]
+python tools/layer_bench.py --upblur [--batch 8] [--repeats 5]: per up-sampling layer, the two-launch forward (all-phase UP conv +
+blur launch with the fused activation) against the one-launch form (w2e_modconv_upblur), alternating, `repeats` runs each."""
 import argparse
 import os
 import sys
@@ -29,8 +31,50 @@ def timeit(fn, iters):
     return a.elapsed_time(b) / iters
 
 
+def upblur_table(batch, iters, repeats, sel):
+    """The pair (conv + blur launch) against the fused form, per up layer from 32^2 inputs up: min / median / max over `repeats`
+    alternating runs of `iters` calls each.  A layer counts as a gain only if the fused form's slowest run beats the pair's fastest."""
+    from where2edit_amd import _lib
+    dev = "cuda"
+    kernel = (torch.outer(torch.tensor([1., 3., 3., 1.]), torch.tensor([1., 3., 3., 1.])) / 64 * 4).to(dev)
+    print(f"batch {batch}: {iters} calls per run, {repeats} alternating runs of each form; ms per call as min / median / max")
+    print(f"{'layer':22s} | {'conv + blur launch':>26s} | {'fused':>26s} | {'median gain':>11s} | fused max < pair min")
+    for i, (cin, cout, h, up) in enumerate(LAYERS):
+        if not up or h < 32 or (sel and i not in sel):
+            continue
+        w = torch.randn(cout, cin, 3, 3, device=dev)
+        fwd = K.conv_pack(w, (cin * 9) ** -0.5, False, False)
+        x = torch.randn(batch, cin, h, h, device=dev)
+        s = torch.randn(batch, cin, device=dev)
+        d = torch.rand(batch, cout, device=dev) + 0.5
+        act = (torch.randn(1, 1, 2 * h, 2 * h, device=dev), torch.randn(1, device=dev), torch.randn(cout, device=dev))
+
+        def pair():
+            t, _ = K._modconv_raw(K.MODE_UP, x, fwd, s, d, h, h)
+            return K._upfirdn2d_raw(t, kernel, 2 * h, 2 * h, 1, 1, 1, 1, True, act=(None,) + act, planar_hw=(2 * h + 1, 2 * h + 1))
+
+        def fused():
+            return K._modconv_upblur_raw(x, fwd, s, d, kernel, h, h, act)
+
+        _lib.set_option("tune_upblur", 1)
+        if not K._upblur_planned(batch, cin, cout, h, h):
+            print(f"{cin:3d}->{cout:3d} @{h:4d} up: the fused form does not take this shape")
+            continue
+        tp, tf = [], []
+        for _ in range(repeats):
+            tp.append(timeit(pair, iters))
+            tf.append(timeit(fused, iters))
+        _lib.set_option("tune_upblur", "")
+        tp.sort(), tf.sort()
+        fmt = lambda t: f"{t[0]:8.3f} {t[len(t) // 2]:8.3f} {t[-1]:8.3f}"  # noqa: E731
+        gain = tp[len(tp) // 2] - tf[len(tf) // 2]
+        print(f"{cin:3d}->{cout:3d} @{h:4d} up      | {fmt(tp)} | {fmt(tf)} | {gain:8.3f} ms | {'yes' if tf[-1] < tp[0] else 'no'}")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--upblur", action="store_true", help="compare conv + blur launch with the one-launch form on the up layers")
+    ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--only", type=str, default="", help="comma list of layer indices")
@@ -43,6 +87,9 @@ def main():
         t0 = time.perf_counter()
         while time.perf_counter() - t0 < args.warm:
             (a @ a).sum().item()
+    if args.upblur:
+        upblur_table(args.batch, args.iters, args.repeats, [int(i) for i in args.only.split(',')] if args.only else None)
+        return
     B = args.batch
     dev = "cuda"
     tot = {"fwd": [0.0, 0.0], "bwd": [0.0, 0.0]}

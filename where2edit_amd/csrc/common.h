@@ -17,6 +17,7 @@ struct Options {
     int deterministic;   // 1 = no fp32 atomics anywhere: ordered reductions, no split-K (W2E_DETERMINISTIC=1)
     int tune_cfg, tune_cfg_splits, tune_cfg_mode;  // force a conv tile (tests / tools/layer_bench.py); -1 = off
     int tune_upall, tune_dma, tune_fuse;  // -1 = the library's own choice, 0 never, 1 always
+    int tune_upblur;  // the up-sampling conv with the blur in its epilogue (w2e_modconv_upblur): -1 = the measured layers, 0 never, 1 wherever it fits
     int tune_mw;   // matrix waves of the fused Winograd kernel: -1 = 8 wherever N % 64 == 0; 4 = always the 32-channel form
     int tune_xcd;  // XCD-contiguous block ownership in the fused Winograd kernel: -1 / 1 = on (default), 0 = the old round-robin order (A/B).
                    // (Measured and not kept for the direct kernel: same FETCH_SIZE, same time -- profiles/r05_xcd_map_ab.txt)

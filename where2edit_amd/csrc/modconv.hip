@@ -61,6 +61,8 @@ struct ConvParams {
     int in_off;          // DOWN: the input origin is shifted by in_off (-1 = a stride-2 convolution with padding 1 of an in_h x in_w image)
     int splits, k_per;  // split-K: workgroup ks reduces channels [ks*k_per, (ks+1)*k_per) and adds atomically
     unsigned long long* stamps;  // tuning aid (W2E_TUNE_CLOCK): per workgroup {s_memtime, s_memrealtime} at start and end
+    const float* fir;    // UPB: the 4x4 FIR taps (as w2e_upfirdn2d takes them; applied flipped)
+    int vec4;            // UPB: y and noise are 16-byte aligned and 2W % 4 == 0 -- a lane's 4 output columns move as one float4
 };
 
 enum { EPI_PLAIN = 0, EPI_ACT = 1, EPI_DOT = 2, EPI_PRELU = 3 };
@@ -374,7 +376,9 @@ __device__ __forceinline__ void upconv_border(const ConvParams& p, float* smem, 
     }
 }
 
-template <int MODE, int EPI, int NOB, int NPB, int WO, int WP, int KC, int DMA>
+// UPB (all-phase UP, tile {1,8,1,8}, LDS-DMA pipeline): the 4x4 blur and the StyledConv epilogue run in the tile's own epilogue, over
+// overlapping tiles -- see the block after the K loop.
+template <int MODE, int EPI, int NOB, int NPB, int WO, int WP, int KC, int DMA, int UPB = 0>
 __global__ __launch_bounds__(64 * WO * WP, 2) void modconv_kernel(ConvParams p) {
     constexpr int NT = 64 * WO * WP;  // 256 threads (small tiles, 2 workgroups/CU) or 512 (big tiles, 1/CU)
     constexpr int TN = 32 * NOB * WO;
@@ -394,7 +398,7 @@ __global__ __launch_bounds__(64 * WO * WP, 2) void modconv_kernel(ConvParams p) 
     const int wo = wave / WP, wpx = wave % WP;
 
     int bid = blockIdx.x;
-    if (is_up(MODE)) {
+    if (is_up(MODE) && !UPB) {
         if (bid < p.border_wgs) {  // uniform per workgroup
             if (W2E_SKIP(p, 32)) return;  // tuning aid: price the border workgroups
             upconv_border<NT>(p, smem, bid);
@@ -423,7 +427,9 @@ __global__ __launch_bounds__(64 * WO * WP, 2) void modconv_kernel(ConvParams p) 
     const int b = bid % p.batch;
     const int nt = bid / p.batch;
     const int n0 = nt * TN;
-    const int r0 = ty * p.th, c0 = tx * p.tw;
+    // UPB: tiles overlap by a one-position halo on every side -- a th x tw tile owns (th-2) x (tw-2) input positions; positions -1 and
+    // H / W stage as zeros like any other out-of-image input, which is the blur's zero padding and T's last row / column at once
+    const int r0 = UPB ? ty * (p.th - 2) - 1 : ty * p.th, c0 = UPB ? tx * (p.tw - 2) - 1 : tx * p.tw;
 
     // per-lane LDS base of each of the wave's NPB pixel blocks (pixel coordinates are recomputed in the
     // epilogue instead of being kept live across the MFMA loop)
@@ -432,7 +438,7 @@ __global__ __launch_bounds__(64 * WO * WP, 2) void modconv_kernel(ConvParams p) 
     for (int pb = 0; pb < NPX; ++pb) {
         const int m = (wpx * NPX + pb) * 32 + j;
         const int ly = m >> p.tw_log2, lx = m & (p.tw - 1);
-        const bool ok = ly < p.th && r0 + ly < p.H && c0 + lx < p.W;
+        const bool ok = UPB || (ly < p.th && r0 + ly < p.H && c0 + lx < p.W);  // (UPB: every position of the tile lies inside its patch)
         int off;
         if (MODE == W2E_CONV_SAME) off = ly * p.pw + lx;            // patch origin (r0-1, c0-1); tap (a,b): +a*pw+b
         else if (is_up(MODE)) off = (ly + 1) * p.pw + lx + 1;  // same origin; tap: -(a>>1)*pw-(b>>1)
@@ -834,6 +840,169 @@ __global__ __launch_bounds__(64 * WO * WP, 2) void modconv_kernel(ConvParams p) 
         k_loop(I0{}, I0{});
     }
 
+    // ---- UPB epilogue: the tile's T patch never leaves the CU.  The accumulators go through LDS (the operand stages are free after a
+    // barrier) in 2 groups of 16 channels, scaled by out_scale exactly as the two-launch form stores them: channel c of a group is a
+    // 32 x 64 image (T rows 2*r0 .. 2*r0+31, columns 2*c0 .. 2*c0+63), 128 KB per group (with 8-channel groups all 128 accumulator
+    // registers stay live under the first FIR passes: spills).  480 of the 512 threads then each take one
+    // channel, 4 adjacent output columns and a strip of 14 output rows, walk down the strip with a 7-wide register window per T row
+    // (two ds_read_b128) as upfirdn_stream4_kernel does, and store float4s of the final [B,N,2H,2W] tensor after that kernel's folded
+    // epilogue (gain folded into scale, bias and noise strength; lrelu(e) = max(e, 0.2 e)).  The tile owns output rows
+    // 2*(r0+1) .. +27 and columns 2*(c0+1) .. +59; output (Y,X) reads T rows Y-1 .. Y+2 and columns X-1 .. X+2 (pad 1, flipped taps).
+    if constexpr (UPB) {
+        static_assert(MODE == CONV_UPALL && EPI == EPI_PLAIN && NOB == 1 && NPB == 8 && WO == 1 && WP == 8 && DMA == 1, "the blur epilogue is written for tile {1,8,1,8}");
+        typedef float f32x2 __attribute__((ext_vector_type(2)));
+        typedef float f32x4 __attribute__((ext_vector_type(4)));
+        typedef int i32x4 __attribute__((ext_vector_type(4)));
+        constexpr int TPITCH = 64, CHS = 32 * TPITCH;    // (host: th = 16, tw = 32)
+        constexpr int GCH = 16, SROWS = 14, NSTRIP = 2, QUADS = 15, ITEMS = NSTRIP * GCH * QUADS;  // 2 strips x 16 channels x 15 column quads = 480 work items
+        constexpr unsigned OOB = 0x80000000u;  // (host: every descriptor of this block spans < 2^31 bytes)
+        constexpr float kGainF = 1.4142135623730951f, kSlope = 0.2f;
+        const int out_w = 2 * p.W, out_h = 2 * p.H;
+        const unsigned oplane = (unsigned)out_h * (unsigned)out_w;  // (host: N * oplane * 4 < 2^31)
+        const bool vec = p.vec4 != 0;
+        const bool worker = tid < ITEMS;
+        const int strip = tid / (GCH * QUADS), rem = tid - strip * (GCH * QUADS);
+        const int ch = rem / QUADS, qi = rem - ch * QUADS;
+        const int Y0 = 2 * (r0 + 1) + strip * SROWS, X0 = 2 * (c0 + 1) + 4 * qi;  // >= 0
+        // taps as w2e_upfirdn2d takes them with flip = 1, and their separable form when they have one (uniform)
+        float kr[16], kh[4], kv[4];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) kr[i] = p.fir[15 - i];
+        bool separable = kr[0] != 0.f;
+        {
+            float kmax = 0.f;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) kmax = fmaxf(kmax, fabsf(kr[i]));
+#pragma unroll
+            for (int i = 0; i < 4; ++i) kh[i] = kr[i], kv[i] = separable ? kr[4 * i] / kr[0] : 0.f;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) separable = separable && fabsf(kr[i] - kv[i >> 2] * kh[i & 3]) <= 1e-7f * kmax;
+        }
+        // Everything the epilogue reads from memory is loaded before its first store (see the note on vmcnt below) and parked in LDS
+        // behind the T patch: out_scale of the tile's 32 channels and the noise of its 28 x 60 outputs (rows / columns outside the
+        // image, and a null vector, read as 0 past a descriptor).
+        float* const nzs = smem + GCH * CHS;      // [NSTRIP * SROWS][QUADS] float4
+        float* const oss = nzs + NSTRIP * SROWS * QUADS * 4;  // [32]
+        const bool has_os = p.out_scale != nullptr;
+        const __amdgpu_buffer_rsrc_t rbs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bias ? p.bias : p.x), (short)0, p.bias ? p.N * 4 : 0, 0x00020000);
+        float eb2[2];
+#pragma unroll
+        for (int g = 0; g < 2; ++g) eb2[g] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rbs, (unsigned)(n0 + GCH * g + ch) * 4u, 0, 0)) * kGainF;
+        const float nw = p.noise ? p.noise_w[0] * kGainF : 0.f;
+        const __amdgpu_buffer_rsrc_t rn = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.noise ? p.noise : p.x), (short)0, p.noise ? (int)(oplane * 4u) : 0, 0x00020000);
+        float nzv[4] = {0.f, 0.f, 0.f, 0.f};
+        float osv = 1.f;
+        {
+            const int nq = tid / QUADS, ni = tid - nq * QUADS;  // noise item: output row nq (0..27), column quad ni
+            const int ny = 2 * (r0 + 1) + nq, nx = 2 * (c0 + 1) + 4 * ni;
+            const unsigned no = (nq < NSTRIP * SROWS && ny < out_h && nx < out_w) ? ((unsigned)ny * (unsigned)out_w + (unsigned)nx) * 4u : OOB;
+            if (vec) {
+                const f32x4 n4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rn, no, 0, 0));
+                nzv[0] = n4[0], nzv[1] = n4[1], nzv[2] = n4[2], nzv[3] = n4[3];
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    nzv[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rn, (no != OOB && nx + e < out_w) ? no + 4u * e : OOB, 0, 0));
+            }
+            if (has_os && tid < 32) osv = n0 + tid < p.N ? p.out_scale[(int64_t)b * p.N + n0 + tid] : 0.f;
+        }
+        // byte offset of the lane's column group in the strip's first output row of a plane; per row: + q * out_w * 4
+        const bool col_ok = worker && X0 < out_w;
+        const unsigned p0 = ((unsigned)Y0 * (unsigned)out_w + (unsigned)X0) * 4u;
+        const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(p.y + (int64_t)b * p.N * oplane, (short)0, (int)((unsigned)p.N * oplane * 4u), 0x00020000);
+        __syncthreads();  // the K loop's last operand reads are done: LDS is free
+        if (tid < NSTRIP * SROWS * QUADS) *reinterpret_cast<f32x4*>(nzs + 4 * tid) = f32x4{nzv[0], nzv[1], nzv[2], nzv[3]};
+        if (tid < 32) oss[tid] = osv;
+        // group G of the accumulators -> LDS: registers 8G .. 8G+7 of both lane halves are the group's 16 channels; the two column
+        // phases of a position are adjacent columns of T: one 8-byte write per (register, pixel block, row phase)
+        auto put = [&](auto gc) __attribute__((always_inline)) {
+            constexpr int G = decltype(gc)::value;
+#pragma unroll
+            for (int rr = 0; rr < 8; ++rr) {
+                const int r = 8 * G + rr;
+                const int c = (rr & 3) + 8 * (rr >> 2) + 4 * half;  // channel inside the group
+                const float osr = oss[GCH * G + c];
+                float* tc = smem + c * CHS + 2 * j;
+#pragma unroll
+                for (int pb = 0; pb < 2; ++pb)
+#pragma unroll
+                    for (int py = 0; py < 2; ++py) {
+                        const int row = 2 * (wave * 2 + pb) + py;
+                        f32x2 v;
+                        v[0] = acc[0][(2 * py + 0) * 2 + pb][r] * osr;
+                        v[1] = acc[0][(2 * py + 1) * 2 + pb][r] * osr;
+                        *reinterpret_cast<f32x2*>(tc + row * TPITCH) = v;
+                    }
+            }
+        };
+        auto fir = [&](auto sep_c, int g, float eb) __attribute__((always_inline)) {
+            constexpr bool SEP = decltype(sep_c)::value;
+            const bool ch_ok = n0 + GCH * g + ch < p.N;
+            const unsigned choff = (unsigned)(n0 + GCH * g + ch) * oplane * 4u;
+            const float* tb = smem + ch * CHS + (strip * SROWS + 1) * TPITCH + 4 * qi;
+            f32x4 o[4];
+#pragma unroll
+            for (int s = 0; s < 4; ++s) o[s] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int k = 0; k < SROWS + 3; ++k) {  // T row (strip's first output row) + k feeds output rows k-3 .. k with tap rows 3 .. 0
+                const f32x4 wa = *reinterpret_cast<const f32x4*>(tb + k * TPITCH), wb = *reinterpret_cast<const f32x4*>(tb + k * TPITCH + 4);
+                const float w[8] = {wa[0], wa[1], wa[2], wa[3], wb[0], wb[1], wb[2], wb[3]};  // output column e reads w[e+1 .. e+4]
+                if (SEP) {
+                    f32x4 h;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) h[e] = kh[0] * w[e + 1] + kh[1] * w[e + 2] + kh[2] * w[e + 3] + kh[3] * w[e + 4];
+#pragma unroll
+                    for (int a = 0; a < 4; ++a)
+                        if (k - a >= 0 && k - a < SROWS) o[(k - a) & 3] += kv[a] * h;
+                } else {
+#pragma unroll
+                    for (int a = 0; a < 4; ++a)
+                        if (k - a >= 0 && k - a < SROWS) {
+#pragma unroll
+                            for (int e = 0; e < 4; ++e)
+                                o[(k - a) & 3][e] += kr[4 * a] * w[e + 1] + kr[4 * a + 1] * w[e + 2] + kr[4 * a + 2] * w[e + 3] + kr[4 * a + 3] * w[e + 4];
+                        }
+                }
+                if (k >= 3) {  // output row q = k - 3 is complete
+                    const int q = k - 3;
+                    const f32x4 acc4 = o[q & 3];
+                    o[q & 3] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    const f32x4 nz = *reinterpret_cast<const f32x4*>(nzs + ((strip * SROWS + q) * QUADS + qi) * 4);
+                    float v[4];  // (scalars: with the results kept as elements of a vector, the compiler stored element 0 four times below)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float t = acc4[e] * kGainF + eb + nw * nz[e];
+                        v[e] = fmaxf(t, t * kSlope);
+                    }
+                    const unsigned vo = (ch_ok && col_ok && Y0 + q < out_h) ? p0 + choff + (unsigned)(q * out_w) * 4u : OOB;
+                    if (vec) {
+                        f32x4 v4;
+                        v4[0] = v[0], v4[1] = v[1], v4[2] = v[2], v4[3] = v[3];
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, v4), ry, vo, 0, 0);
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v[e]), ry, (vo != OOB && X0 + e < out_w) ? vo + 4u * e : OOB, 0, 0);
+                    }
+                }
+            }
+        };
+        using B0 = std::integral_constant<bool, false>;
+        using B1 = std::integral_constant<bool, true>;
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            __syncthreads();  // out_scale is in LDS / the previous group's window reads are done
+            if (g == 0) put(std::integral_constant<int, 0>{});
+            else put(std::integral_constant<int, 1>{});
+            __syncthreads();
+            if (worker) {
+                if (separable) fir(B1{}, g, eb2[g]);
+                else fir(B0{}, g, eb2[g]);
+            }
+        }
+        return;
+    }
+
     // ---- epilogue
     // (EPI_ACT: the activation's gain sqrt(2) is folded into out_scale, bias and the noise strength -- lrelu(v)*g = lrelu(v*g), g > 0)
     const float nw = (EPI == EPI_ACT && p.noise) ? p.noise_w[0] * 1.4142135623730951f : 0.f;
@@ -1006,13 +1175,13 @@ struct TileCfg {
     int nob, npb, wo, wp;
 };
 
-template <int MODE, int EPI, int NOB, int NPB, int WO, int WP, int KC, int DMA = 0>
+template <int MODE, int EPI, int NOB, int NPB, int WO, int WP, int KC, int DMA = 0, int UPB = 0>
 static void launch_cfg(const ConvParams& p, int grid, size_t lds, hipStream_t s) {
     if (lds > 64 * 1024) {  // dynamic LDS above 64 KB is opt-in per kernel and per device (gfx950: 160 KB per CU)
         static unsigned done = 0;
-        big_lds_once((const void*)modconv_kernel<MODE, EPI, NOB, NPB, WO, WP, KC, DMA>, &done);
+        big_lds_once((const void*)modconv_kernel<MODE, EPI, NOB, NPB, WO, WP, KC, DMA, UPB>, &done);
     }
-    modconv_kernel<MODE, EPI, NOB, NPB, WO, WP, KC, DMA><<<grid, 64 * WO * WP, lds, s>>>(p);
+    modconv_kernel<MODE, EPI, NOB, NPB, WO, WP, KC, DMA, UPB><<<grid, 64 * WO * WP, lds, s>>>(p);
 }
 
 // The LDS-DMA pipeline is instantiated for the tiles the high-resolution layers use; other tiles keep the register pipeline.
@@ -1502,4 +1671,77 @@ extern "C" int w2e_conv3x3(int mode, const float* x, const float* wp, const floa
     W2E_REQUIRE(!(prelu && mode == W2E_CONV_UP), "conv3x3: no bias / PReLU epilogue in UP mode");
     return conv_impl(mode, x, wp, in_scale, out_scale, y, batch, k_ch, n_ch, h, w, 0, nullptr, nullptr, bias, nullptr, nullptr,
                      slope, prelu, down_pad, stream);
+}
+
+// ---- the all-phase UP conv with the 4x4 blur and the StyledConv epilogue in the tile's epilogue (modconv_kernel UPB): one launch
+// writes the final [B,N,2H,2W] tensor, the intermediate T never exists.  Tile {1,8,1,8} as 16 x 32 input positions, of which a tile owns
+// 14 x 30 (the rest is the recomputed halo of the blur): 1.30x the K-loop work of the two-launch form at 512^2, 1.5x at 64^2.
+namespace w2e {
+constexpr int UPB_TH = 16, UPB_TW = 32;
+
+// Why the fused form cannot take a launch, or nullptr.  (fp32 only; no split-K: the blur needs the complete sum.)
+static const char* upblur_refusal(const Options& opt, int batch, int k_ch, int n_ch, int h, int w) {
+    if (batch < 0 || k_ch <= 0 || n_ch <= 0 || h <= 0 || w <= 0) return "bad dims";
+    if (opt.conv_precision != 0) return "conv_precision = bf16x3 keeps the two-launch form";
+    if (opt.tune_cfg >= 0 && opt.tune_cfg_splits > 1 && (opt.tune_cfg_mode < 0 || opt.tune_cfg_mode == W2E_CONV_UP)) return "split-K keeps the two-launch form";
+    if (((int64_t)k_ch + 8) * h * w * 4 >= ((int64_t)1 << 32)) return "one image of the input exceeds 4 GB";
+    if ((int64_t)n_ch * 4 * h * w * 4 >= ((int64_t)1 << 31)) return "one image of the output exceeds 2 GB";
+    if ((int64_t)batch * ceil_div(n_ch, 32) * ceil_div(h, UPB_TH - 2) * ceil_div(w, UPB_TW - 2) >= ((int64_t)1 << 31)) return "too many tiles";
+    return nullptr;
+}
+
+// tune_upblur = -1: the layers where the fused form measured faster than conv + blur launch by more than the spread of repeated runs
+// (tools/layer_bench.py --upblur, profiles/upblur_layer_bench.txt)
+static bool upblur_auto(const Options& opt, int k_ch, int n_ch, int h, int w) {
+    if (opt.tune_cfg >= 0 || opt.tune_upall == 0 || opt.tune_dma == 0) return false;  // a forced tile / form is what the caller wants to see run
+    return k_ch <= 64 && n_ch <= 32 && (int64_t)h * w >= 512 * 512;
+}
+}  // namespace w2e
+
+extern "C" int w2e_modconv_upblur_plan(int batch, int k_ch, int n_ch, int h, int w, int* fused) {
+    W2E_REQUIRE(fused != nullptr, "modconv_upblur_plan: null argument");
+    const Options& opt = options();
+    *fused = 0;
+    if (opt.tune_upblur == 0 || upblur_refusal(opt, batch, k_ch, n_ch, h, w)) return 0;
+    *fused = (opt.tune_upblur > 0 || upblur_auto(opt, k_ch, n_ch, h, w)) ? 1 : 0;
+    return 0;
+}
+
+extern "C" int w2e_modconv_upblur(const float* x, const float* wp, const float* in_scale, const float* out_scale, const float* kern,
+                                  float* y, int batch, int k_ch, int n_ch, int h, int w, const float* noise, const float* noise_w,
+                                  const float* bias, void* stream) {
+    W2E_REQUIRE(x && wp && kern && y, "modconv_upblur: null tensor");
+    W2E_REQUIRE(!noise || noise_w, "modconv_upblur: noise without noise_w");
+    const Options& opt = options();
+    const char* why = upblur_refusal(opt, batch, k_ch, n_ch, h, w);
+    W2E_REQUIRE(!why, "modconv_upblur: %s (K %d N %d %dx%d B %d)", why, k_ch, n_ch, h, w, batch);
+    if (batch == 0) return 0;
+    ConvParams p{};
+    p.x = x, p.wp = wp, p.in_scale = in_scale, p.out_scale = out_scale, p.y = y;
+    p.noise = noise, p.noise_w = noise_w, p.bias = bias, p.fir = kern;
+    p.batch = batch, p.K = k_ch, p.N = n_ch, p.H = h, p.W = w;
+    p.in_h = h, p.in_w = w, p.out_h = 2 * h, p.out_w = 2 * w;
+    p.th = UPB_TH, p.tw = UPB_TW, p.tw_log2 = 5;
+    p.tiles_x = (int)ceil_div(w, UPB_TW - 2), p.tiles_y = (int)ceil_div(h, UPB_TH - 2), p.tiles_n = (int)ceil_div(n_ch, 32);
+    p.ph = UPB_TH + 1, p.pw = UPB_TW + 1;
+    p.plane = (p.ph * p.pw + 15) & ~15;  // whole DMA wave-instructions per plane
+    p.pw_magic = (unsigned)(((uint64_t)1 << 32) / (unsigned)p.pw + 1);
+    p.splits = 1, p.k_per = (int)(ceil_div(k_ch, 8) * 8);
+    p.vec4 = ((2 * w) % 4 == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)noise & 15) == 0) ? 1 : 0;
+    // two DMA stages + the in_scale table during the K loop, one 16-channel group of the T patch (32 x 64 floats each) afterwards
+    // (+ the tile's noise patch, 28 x 60, and its 32 out_scale values)
+    size_t lds = sizeof(float) * (2 * ((size_t)8 * 9 * 32 + (size_t)8 * p.plane) + (size_t)((k_ch + 7) / 8) * 8);
+    const int groups = 2;
+    const size_t lds_epi = sizeof(float) * (16 * 32 * 64 + 28 * 60 + 32);
+    if (lds < lds_epi) lds = lds_epi;
+    W2E_REQUIRE(lds <= 160 * 1024, "modconv_upblur: K = %d needs %zu B of LDS", k_ch, lds);
+    const int64_t grid = (int64_t)p.tiles_x * p.tiles_y * p.tiles_n * batch;
+    if (opt.tune_print) {  // the layer line every conv launch prints (it is still one of the step's 3x3 conv launches), then a variant line
+                           // of its own format: the census of tests/test_gpu_upblur.py keys on it
+        fprintf(stderr, "modconv mode %d (all-phase) K %d N %d %dx%d B %d -> cfg 11 splits 1\n", W2E_CONV_UP, k_ch, n_ch, h, w, batch);
+        fprintf(stderr, "modconv upblur variant cfg 11 th %d tw %d groups %d vec %d K %d N %d %dx%d B %d\n", p.th, p.tw, groups, p.vec4, k_ch, n_ch, h, w, batch);
+    }
+    launch_cfg<CONV_UPALL, EPI_PLAIN, 1, 8, 1, 8, 8, 1, 1>(p, (int)grid, lds, (hipStream_t)stream);
+    W2E_LAUNCH_CHECK("modconv_upblur");
+    return 0;
 }

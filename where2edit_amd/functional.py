@@ -420,6 +420,31 @@ def _modconv_raw(mode, x, wp, in_scale, out_scale, h, w, act=None, dot_with=None
     return y, dot
 
 
+def _upblur_planned(b, k, n, h, w):
+    """Whether the library takes an up-sampling StyledConv of this shape as ONE launch (w2e_modconv_upblur_plan: option tune_upblur,
+    fp32 only, the layers it measured faster on)."""
+    fused = ctypes.c_int(0)
+    call("w2e_modconv_upblur_plan", b, k, n, h, w, ctypes.byref(fused))
+    return bool(fused.value)
+
+
+def _modconv_upblur_raw(x, wp, in_scale, out_scale, kernel, h, w, act):
+    """One call of w2e_modconv_upblur: lrelu(blur(out_scale * conv_transpose(Wp, in_scale * x)) + nw*noise + bias) * sqrt2 as
+    [b,n,2h,2w]; the (2h+1)x(2w+1) transposed-conv image is never written.  act = (noise, noise_w, bias)."""
+    b, k = x.shape[0], x.shape[1]
+    n = wp.shape[3]
+    if wp.shape[0] != (k + 7) // 8:
+        raise RuntimeError(f"modconv: packed weight holds {wp.shape[0]} 8-channel groups, input has {k} channels")
+    noise, noise_w, bias = act
+    y = torch.empty((b, n, 2 * h, 2 * w), device=x.device, dtype=torch.float32)
+    sp = profiling.span("modconv3x3", 2.0 * b * k * n * 9 * h * w)  # algorithmic FLOPs: the recomputed halo is not useful work
+    call("w2e_modconv_upblur", ptr(x), ptr(wp), ptr(in_scale), ptr(out_scale), ptr(kernel), ptr(y), b, k, n, h, w,
+         ptr(noise), ptr(noise_w), ptr(bias), stream_ptr())
+    if sp is not None:
+        sp.end()
+    return y
+
+
 def _channel_dot(a, b, out=None):
     """[B,C] = sum_p a*b per plane (w2e_channel_sums: one wave per plane, fixed reduction order)."""
     n, c = a.shape[0], a.shape[1]
@@ -564,7 +589,9 @@ class _StyledConv(torch.autograd.Function):
         if wsq is not None:
             d = d_pre if d_pre is not None else demod_coefficients(s, wsq)
         act = (noise, noise_w, bias) if fuse_act else None
-        if upsample:
+        if upsample and fuse_act and tuple(blur_kernel.shape) == (4, 4) and _upblur_planned(b, cin, wp_f.shape[3], h, w):
+            out = _modconv_upblur_raw(x, wp_f, s, d, blur_kernel, h, w, act)
+        elif upsample:
             t, _ = _modconv_raw(MODE_UP, x, wp_f, s, d, h, w)
             if w >= 16:   # the tile kernel reads the phase-planar layout directly
                 out = _upfirdn2d_raw(t, blur_kernel, 2 * h, 2 * w, 1, 1, 1, 1, True,
