@@ -42,7 +42,8 @@ extern "C" {
  * 4 (DOWN-CENTRE), K8 (w2e_fromrgb_fwd / w2e_fromrgb_bwd_rows / w2e_fromrgb_bwd / w2e_mbstd_fwd / w2e_mbstd_bwd, the Discriminator), and
  * K8's forward-mode entries for the R1 penalty (w2e_fromrgb_jvp / w2e_mbstd_jvp / w2e_mbstd_hvp / w2e_sumsq_rows_parts / w2e_sumsq_rows), and
  * w2e_mask_iou_counts (w2e_attention.h, the mask IoU evaluation).
- * Still 7: w2e_modconv_upblur / w2e_modconv_upblur_plan and the option tune_upblur are additive too */
+ * Still 7: w2e_modconv_upblur / w2e_modconv_upblur_plan and the option tune_upblur are additive too; so are
+ * w2e_modconv_down_rgbfold / w2e_modconv_down_rgbfold_plan and the option tune_rgbfold */
 #define W2E_VERSION 7
 
 int w2e_version(void);
@@ -55,13 +56,13 @@ const char* w2e_last_error(void);
  *                                          cudnn.deterministic=True (attention/run_attention.py:903-904)
  *   "tune_cfg" [W2E_TUNE_CFG] "<cfg>[,<splits>[,<mode>]]" force a conv tile (tests, tools/layer_bench.py); "" = off.  A forced
  *   tile passes the selection's own feasibility filters (LDS, patch slots): one that does not fit a launch fails it
- *   "tune_upall", "tune_dma", "tune_fuse", "tune_upblur", "tune_print", "tune_blur", "tune_gemm_s": kernel-selection aids -- they
+ *   "tune_upall", "tune_dma", "tune_fuse", "tune_upblur", "tune_rgbfold", "tune_print", "tune_blur", "tune_gemm_s": kernel-selection aids -- they
  *   choose between kernels / tiles that compute the same result ("tune_blur": only bit 8, keep the LDS-tile FIR kernels
  *   for wide images; its bits 1/2/4 and "tune_skip" / "tune_clock" drop loads, arithmetic or stores, or synchronise,
  *   and are compiled in ONLY by -DW2E_TUNING: the shipped library ignores them)
  *   "debug_poison" [W2E_DEBUG_POISON] "1": host-side aid -- gradient rows the merged forward declares unused are
  *   filled with NaN instead of being left unwritten, so that a consumer that reads them fails loudly (tests)
- * w2e_get_option reads "conv_precision", "deterministic", "tune_cfg", "tune_upblur", "tuning_build" (1 = compiled with -DW2E_TUNING). */
+ * w2e_get_option reads "conv_precision", "deterministic", "tune_cfg", "tune_upblur", "tune_rgbfold", "tuning_build" (1 = compiled with -DW2E_TUNING). */
 int w2e_set_option(const char* name, const char* value);
 
 /* Row pitch (floats) of the phase planes of the transposed-conv output T for an input W wide: W+1 columns rounded up to 16 floats =
@@ -158,6 +159,28 @@ int w2e_modconv_upblur_plan(int batch, int k_ch, int n_ch, int h, int w, int* fu
 int w2e_modconv_upblur(const float* x, const float* wp, const float* in_scale, const float* out_scale, const float* kern,
                        float* y, int batch, int k_ch, int n_ch, int h, int w, const float* noise, const float* noise_w,
                        const float* bias, void* stream);
+
+/* ---- K1f  the stride-2 input-gradient conv of an up-sampling StyledConv with the ToRGB backward in its dot epilogue --------------
+ * In the generator's backward the W2E_CONV_DOWN launch with dot_with = x (x: the activation of the level below, which also feeds that
+ * level's ToRGB) is followed by w2e_torgb_bwd_actbwd, which reads x and the conv's output again.  This launch does both:
+ *     a          = conv(Wp, in_scale[b,i] * g[b,i])                                   (stride 2, as W2E_CONV_DOWN)
+ *     dot_out[b,o] += sum_p a * x                                                     (unscaled, as w2e_modconv3x3's dot epilogue)
+ *     gpre[b,o,p] = (a * out_scale[b,o] + sum_c w[b,c,o] * gy[b,c,p]) * gain * (x > 0 ? 1 : slope)
+ *     sums3[b,o,:] += (sum_p gpre * pre, sum_p gpre * noise[p], sum_p gpre),  pre = x > 0 ? x/gain : x/(gain*slope)
+ *     gw += the ToRGB style gradient [B,N] (style != NULL: w[b,c,o] = wrgb[c,o] * style[b,o], wrgb the shared [3,N] weight) or the
+ *           per-sample weight gradient [B,3,N] (style == NULL: w = wrgb [B,3,N]) -- sum_p x * gy[b,c,p], as w2e_torgb_bwd_actbwd
+ * x = dot_with [B,N,h,w]; gy [B,3,h,w]; noise [h*w] or NULL; dot_out, sums3 and gw are accumulated with fp32 atomics and must be
+ * ZEROED by the caller.  h,w: the output size, as for W2E_CONV_DOWN (the input g is [B,K,2h+1,2w+1]).  The tile is the one the
+ * dispatcher of w2e_modconv3x3 picks for the shape (or "tune_cfg" forces).  w2e_modconv_down_rgbfold_plan says (host code, no GPU)
+ * whether the library would use the form for a shape -- option "tune_rgbfold" [W2E_TUNE_RGBFOLD]: -1 (default) the levels it
+ * measured faster on, 0 never, 1 wherever it is supported.  Not supported (the plan says 0, the launch is refused): a launch the
+ * dispatcher would split over K, deterministic mode, conv_precision = bf16x3, a tile without this epilogue.  No allocation, no
+ * synchronisation: capture-safe. */
+int w2e_modconv_down_rgbfold_plan(int batch, int k_ch, int n_ch, int h, int w, int* fold);
+int w2e_modconv_down_rgbfold(const float* x, const float* wp, const float* in_scale, const float* out_scale, float* gpre, int batch,
+                             int k_ch, int n_ch, int h, int w, const float* dot_with, float* dot_out, const float* gy,
+                             const float* wrgb, const float* style, const float* noise, float* sums3, float* gw, float slope,
+                             float gain, void* stream);
 
 /* ---- K1w  the FUSED Winograd F(4x4,3x3) form of W2E_CONV_SAME  (model.py:270-274; the same contract as w2e_modconv3x3) -------------
  *     y[b,o] = epilogue(out_scale[b,o] * A^T [ sum_i U[.,o,i] (.) V[.,i,t] ] A)

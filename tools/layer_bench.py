@@ -2,7 +2,9 @@
 """Per-layer microbenchmark of the modulated-conv kernels at the FFHQ-1024 generator's layer shapes
 (HIP events on the launch stream, random data).  python tools/layer_bench.py [--batch 4]
 python tools/layer_bench.py --upblur [--batch 8] [--repeats 5]: per up-sampling layer, the two-launch forward (all-phase UP conv +
-blur launch with the fused activation) against the one-launch form (w2e_modconv_upblur), alternating, `repeats` runs each."""
+blur launch with the fused activation) against the one-launch form (w2e_modconv_upblur), alternating, `repeats` runs each.
+python tools/layer_bench.py --rgbfold [--batch 8] [--repeats 5]: per level 4^2 .. 512^2 of the backward, the pair (stride-2
+input-gradient conv with the dot epilogue, w2e_torgb_bwd_actbwd) against the folded launch (w2e_modconv_down_rgbfold), likewise."""
 import argparse
 import os
 import sys
@@ -71,9 +73,59 @@ def upblur_table(batch, iters, repeats, sel):
         print(f"{cin:3d}->{cout:3d} @{h:4d} up      | {fmt(tp)} | {fmt(tf)} | {gain:8.3f} ms | {'yes' if tf[-1] < tp[0] else 'no'}")
 
 
+def rgbfold_table(batch, iters, repeats, sel):
+    """The pair (DOWN dot conv, ToRGB backward with the activation backward) against the folded launch, per up-sampling layer: the
+    backward of the layer h -> 2h writes level h.  min / median / max over `repeats` alternating runs of `iters` calls each.  A level
+    counts as a gain only if the folded form's slowest run beats the pair's fastest."""
+    from where2edit_amd import _lib
+    from where2edit_amd._lib import call, ptr, stream_ptr
+    dev = "cuda"
+    print(f"batch {batch}: {iters} calls per run, {repeats} alternating runs of each form; ms per call as min / median / max")
+    print(f"{'level (DOWN conv K->N)':26s} | {'dot conv + torgb_bwd_actbwd':>26s} | {'folded':>26s} | {'median gain':>11s} | folded max < pair min")
+    for i, (cin, cout, h, up) in enumerate(LAYERS):
+        if not up or (sel and i not in sel):
+            continue
+        name = f"{cout:3d}->{cin:3d} @{h:4d}"
+        _lib.set_option("tune_rgbfold", 1)
+        planned = K._rgbfold_planned(batch, cout, cin, h, h)
+        _lib.set_option("tune_rgbfold", "")
+        if not planned:
+            print(f"{name:26s} | the folded form does not take this launch (split over K)")
+            continue
+        wt = torch.randn(cout, cin, 3, 3, device=dev)
+        bwd = K.conv_pack(wt, (cin * 9) ** -0.5, True, False)
+        g = torch.randn(batch, cout, 2 * h + 1, 2 * h + 1, device=dev)
+        x = torch.randn(batch, cin, h, h, device=dev)
+        s = torch.randn(batch, cin, device=dev)
+        d = torch.rand(batch, cout, device=dev) + 0.5
+        gy = torch.randn(batch, 3, h, h, device=dev)
+        wsc, style = torch.randn(3, cin, device=dev), torch.randn(batch, cin, device=dev)
+        noise = torch.randn(1, 1, h, h, device=dev)
+        gx, gpre = torch.empty_like(x), torch.empty_like(x)
+        dot, gw, sums3 = torch.zeros(batch, cin, device=dev), torch.zeros(batch, cin, device=dev), torch.zeros(batch, cin, 3, device=dev)
+
+        def pair():
+            K._modconv_raw(K.MODE_DOWN, g, bwd, d, s, h, h, dot_with=x, out=gx, dot_out=dot)
+            call("w2e_torgb_bwd_actbwd", ptr(x), ptr(wsc), ptr(style), ptr(gy), ptr(gx), ptr(noise), ptr(gpre), ptr(gw), ptr(sums3),
+                 batch, cin, h, h, 0.2, K.SQRT2, stream_ptr())
+
+        def folded():
+            K._modconv_down_rgbfold_raw(g, bwd, d, s, h, h, x, gy, wsc, style, noise, out=gpre, dot_out=dot, sums3=sums3, gw=gw)
+
+        tp, tf = [], []
+        for _ in range(repeats):
+            tp.append(timeit(pair, iters))
+            tf.append(timeit(folded, iters))
+        tp.sort(), tf.sort()
+        fmt = lambda t: f"{t[0]:8.3f} {t[len(t) // 2]:8.3f} {t[-1]:8.3f}"  # noqa: E731
+        gain = tp[len(tp) // 2] - tf[len(tf) // 2]
+        print(f"{name:26s} | {fmt(tp)} | {fmt(tf)} | {gain:8.3f} ms | {'yes' if tf[-1] < tp[0] else 'no'}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--upblur", action="store_true", help="compare conv + blur launch with the one-launch form on the up layers")
+    ap.add_argument("--rgbfold", action="store_true", help="compare (DOWN dot conv, torgb_bwd_actbwd) with the folded launch per level")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--iters", type=int, default=5)
@@ -89,6 +141,9 @@ def main():
             (a @ a).sum().item()
     if args.upblur:
         upblur_table(args.batch, args.iters, args.repeats, [int(i) for i in args.only.split(',')] if args.only else None)
+        return
+    if args.rgbfold:
+        rgbfold_table(args.batch, args.iters, args.repeats, [int(i) for i in args.only.split(',')] if args.only else None)
         return
     B = args.batch
     dev = "cuda"

@@ -40,6 +40,8 @@ _PROTOS = {
     "w2e_modconv3x3": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "w2e_modconv_upblur_plan": (_I, [_I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int)]),
     "w2e_modconv_upblur": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "w2e_modconv_down_rgbfold_plan": (_I, [_I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int)]),
+    "w2e_modconv_down_rgbfold": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _F, _P]),
     "w2e_wino_weights_fused": (_I, [_P, _P, _I, _I, _P]),
     "w2e_wino_fused": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
     "w2e_wino_gemm_plan": (_I, [_I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64)]),

@@ -18,6 +18,7 @@ struct Options {
     int tune_cfg, tune_cfg_splits, tune_cfg_mode;  // force a conv tile (tests / tools/layer_bench.py); -1 = off
     int tune_upall, tune_dma, tune_fuse;  // -1 = the library's own choice, 0 never, 1 always
     int tune_upblur;  // the up-sampling conv with the blur in its epilogue (w2e_modconv_upblur): -1 = the measured layers, 0 never, 1 wherever it fits
+    int tune_rgbfold;  // the ToRGB backward in the stride-2 dgrad conv's dot epilogue (w2e_modconv_down_rgbfold): -1 = the measured levels, 0 never, 1 wherever supported
     int tune_mw;   // matrix waves of the fused Winograd kernel: -1 = 8 wherever N % 64 == 0; 4 = always the 32-channel form
     int tune_xcd;  // XCD-contiguous block ownership in the fused Winograd kernel: -1 / 1 = on (default), 0 = the old round-robin order (A/B).
                    // (Measured and not kept for the direct kernel: same FETCH_SIZE, same time -- profiles/r05_xcd_map_ab.txt)

@@ -63,9 +63,17 @@ struct ConvParams {
     unsigned long long* stamps;  // tuning aid (W2E_TUNE_CLOCK): per workgroup {s_memtime, s_memrealtime} at start and end
     const float* fir;    // UPB: the 4x4 FIR taps (as w2e_upfirdn2d takes them; applied flipped)
     int vec4;            // UPB: y and noise are 16-byte aligned and 2W % 4 == 0 -- a lane's 4 output columns move as one float4
+    // EPI_DOT_RGB (w2e_modconv_down_rgbfold): the ToRGB backward of the level this DOWN launch writes, and its producer's activation backward
+    const float* rgb_gy;     // [B,3,H,W] gradient of the ToRGB output
+    const float* rgb_w;      // rgb_style ? shared [3,N] scale*W : per-sample [B,3,N]
+    const float* rgb_style;  // [B,N] or null
+    const float* rgb_noise;  // [H*W] or null: the producing StyledConv's noise plane
+    float* rgb_sums3;        // [B,N,3], zeroed: sum g*pre, sum g*noise, sum g
+    float* rgb_gw;           // zeroed: rgb_style ? the style gradient [B,N] : the weight gradient [B,3,N]
+    float rgb_slope, rgb_gain;
 };
 
-enum { EPI_PLAIN = 0, EPI_ACT = 1, EPI_DOT = 2, EPI_PRELU = 3 };
+enum { EPI_PLAIN = 0, EPI_ACT = 1, EPI_DOT = 2, EPI_PRELU = 3, EPI_DOT_RGB = 4 };
 
 // Internal variant of W2E_CONV_UP chosen by the host per layer: a workgroup computes ALL FOUR output phases of a
 // (4x smaller) input-pixel tile from one staged patch and all 9 taps -- the NPB accumulator columns of a wave are
@@ -1003,6 +1011,156 @@ __global__ __launch_bounds__(64 * WO * WP, 2) void modconv_kernel(ConvParams p) 
         return;
     }
 
+    // ---- EPI_DOT_RGB (DOWN only, no split-K): EPI_DOT with the ToRGB backward of the level this launch writes and the activation backward
+    // of the StyledConv that produced dot_with = x, applied to the value before it is stored (w2e_modconv_down_rgbfold):
+    //   dot += a*x;  v = a*out_scale + sum_c w_c*gy_c[p];  g = v*gain*(x > 0 ? 1 : slope) -> y;
+    //   sums3 += (g*pre, g*noise[p], g), pre = x*(x > 0 ? 1/gain : 1/(gain*slope));  u_c += x*gy_c[p]
+    // -- what torgb_bwd_kernel<., true, true> computes from a second pass over x and this launch's output.  Same two-pass shape as
+    // EPI_DOT: per 32-channel block, pass 1 loads x four rows at a time, takes the seven per-row sums and replaces the accumulator
+    // row (dead once its dot term is taken) with g; pass 2 only stores.  gy and the noise are loaded once per lane pixel.  The 7 x 4 partial
+    // sums of a row group are joined over the 32 lanes of a row by ONE reduce-scatter butterfly (28 cross-lane moves: each step halves
+    // the values a lane carries; seven independent 5-step butterflies per row would be 140), after which 28 of the 32 lanes hold one
+    // finished sum each and add it to red[7][TN] in LDS; one global atomicAdd per (b, o) and quantity at the end.
+    if constexpr (EPI == EPI_DOT_RGB) {
+        static_assert(MODE == W2E_CONV_DOWN && !UPB, "the ToRGB-backward epilogue is instantiated for DOWN only");
+        constexpr int NQ = 7, RG = 4;
+        constexpr unsigned OOB = 0xfffffff0u;
+        float* const red = smem;  // [NQ][TN] (reuses the weight tile after a barrier)
+        __syncthreads();
+        for (int e = tid; e < NQ * TN; e += NT) red[e] = 0.f;
+        __syncthreads();
+        const unsigned plane_bytes = (unsigned)(p.out_h * p.out_w) * 4u;
+        bool valid[NPB];
+        unsigned poff[NPB], yoff[NPB];  // byte offset of the lane's pixel inside a plane / inside the image (+ 4 planes for the upper lane-half)
+#pragma unroll
+        for (int pb = 0; pb < NPB; ++pb) {
+            const int m = (wpx * NPB + pb) * 32 + j;
+            const int ly = m >> p.tw_log2, lx = m & (p.tw - 1);
+            valid[pb] = ly < p.th && r0 + ly < p.H && c0 + lx < p.W;
+            poff[pb] = valid[pb] ? (unsigned)((r0 + ly) * p.out_w + c0 + lx) * 4u : OOB;
+            yoff[pb] = valid[pb] ? poff[pb] + (unsigned)(4 * half) * plane_bytes : OOB;
+        }
+        const bool has_os = p.out_scale != nullptr, styled = p.rgb_style != nullptr, has_nz = p.rgb_noise != nullptr;
+        const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
+            p.y + (int64_t)b * p.N * (p.out_h * p.out_w), (short)0, (int)((unsigned)p.N * plane_bytes), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float*>(p.dot_with + (int64_t)b * p.N * (p.out_h * p.out_w)), (short)0, (int)((unsigned)p.N * plane_bytes), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float*>(p.rgb_gy + (int64_t)b * 3 * (p.out_h * p.out_w)), (short)0, (int)(3u * plane_bytes), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rn = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float*>(has_nz ? p.rgb_noise : p.x), (short)0, has_nz ? (int)plane_bytes : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t ros = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float*>(has_os ? p.out_scale + (int64_t)b * p.N : p.x), (short)0, has_os ? p.N * 4 : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rwt = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float*>(styled ? p.rgb_w : p.rgb_w + (int64_t)b * 3 * p.N), (short)0, 3 * p.N * 4, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rst = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float*>(styled ? p.rgb_style + (int64_t)b * p.N : p.x), (short)0, styled ? p.N * 4 : 0, 0x00020000);
+        float g0[NPB], g1[NPB], g2[NPB], nz[NPB];  // pixels outside the tile / image read 0 past the descriptors
+#pragma unroll
+        for (int pb = 0; pb < NPB; ++pb) {
+            g0[pb] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rg, poff[pb], 0, 0));
+            g1[pb] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rg, poff[pb], plane_bytes, 0));
+            g2[pb] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rg, poff[pb], 2u * plane_bytes, 0));
+            nz[pb] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rn, poff[pb], 0, 0));
+        }
+        const float g_pos = p.rgb_gain, g_neg = p.rgb_gain * p.rgb_slope, i_pos = 1.f / p.rgb_gain, i_neg = 1.f / (p.rgb_gain * p.rgb_slope);
+        const bool b16 = (j & 16) != 0, b8 = (j & 8) != 0, b4 = (j & 4) != 0, b2 = (j & 2) != 0, b1 = (j & 1) != 0;
+        // the (quantity, row) a lane ends up owning after the reduce-scatter: each step keeps the upper half of the values where its bit is set
+        const int own7 = (b1 ? 1 : 0) + (b2 ? 2 : 0) + (b4 ? 4 : 0);  // 7 = the padding slot of the 7 -> 4 step
+        const int own = own7 + (b8 ? 7 : 0) + (b16 ? 14 : 0);         // = quantity * RG + row of the group
+#pragma unroll
+        for (int ob = 0; ob < NOB; ++ob) {
+            const int ob0 = (wo * NOB + ob) * 32;
+            // g takes the place of the accumulator row by row as the rows die -- in scalars, not as elements written back into the
+            // accumulator vectors: for those the compiler stored element 0 sixteen times below (as in the UPB epilogue's note)
+            float gq[16][NPB];
+#pragma unroll
+            for (int r4 = 0; r4 < 16; r4 += RG) {  // pass 1
+                float xv[RG][NPB], osr[RG], w0[RG], w1[RG], w2[RG];
+                bool ov[RG];
+#pragma unroll
+                for (int rr = 0; rr < RG; ++rr) {
+                    const int ch = ((r4 + rr) & 3) + 8 * ((r4 + rr) >> 2);  // the row's channel for lane-half 0
+                    const unsigned soff = (unsigned)(n0 + ob0 + ch) * plane_bytes;
+#pragma unroll
+                    for (int pb = 0; pb < NPB; ++pb)
+                        xv[rr][pb] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rd, yoff[pb], soff, 0));
+                    const int o = n0 + ob0 + ch + 4 * half;
+                    ov[rr] = o < p.N;
+                    const unsigned co = ov[rr] ? (unsigned)o * 4u : OOB;  // channels >= N: every per-channel vector reads 0
+                    osr[rr] = has_os ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ros, co, 0, 0)) : 1.f;
+                    w0[rr] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rwt, co, 0, 0));
+                    w1[rr] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rwt, co, (unsigned)p.N * 4u, 0));
+                    w2[rr] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rwt, co, (unsigned)p.N * 8u, 0));
+                    if (styled) {
+                        const float st = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rst, co, 0, 0));
+                        w0[rr] *= st, w1[rr] *= st, w2[rr] *= st;
+                    }
+                }
+                float val[NQ * RG + 4];
+#pragma unroll
+                for (int i = 0; i < NQ * RG + 4; ++i) val[i] = 0.f;
+#pragma unroll
+                for (int rr = 0; rr < RG; ++rr) {
+                    const int r = r4 + rr;
+#pragma unroll
+                    for (int pb = 0; pb < NPB; ++pb) {
+                        const float a = (ov[rr] && valid[pb]) ? acc[ob][pb][r] : 0.f;
+                        const float x = xv[rr][pb];
+                        const bool pos = x > 0.f;
+                        val[0 * RG + rr] += a * x;
+                        const float v = a * osr[rr] + w0[rr] * g0[pb] + w1[rr] * g1[pb] + w2[rr] * g2[pb];
+                        const float g = v * (pos ? g_pos : g_neg);
+                        gq[r][pb] = g;
+                        val[1 * RG + rr] += g * (x * (pos ? i_pos : i_neg));
+                        val[2 * RG + rr] += g * nz[pb];
+                        val[3 * RG + rr] += g;
+                        val[4 * RG + rr] += x * g0[pb];
+                        val[5 * RG + rr] += x * g1[pb];
+                        val[6 * RG + rr] += x * g2[pb];
+                    }
+                }
+                // reduce-scatter over the 32 lanes of the half: 28 -> 14 -> 7 (-> 8) -> 4 -> 2 -> 1 values per lane
+#pragma unroll
+                for (int i = 0; i < 14; ++i) val[i] = (b16 ? val[i + 14] : val[i]) + __shfl_xor(b16 ? val[i] : val[i + 14], 16, 64);
+#pragma unroll
+                for (int i = 0; i < 7; ++i) val[i] = (b8 ? val[i + 7] : val[i]) + __shfl_xor(b8 ? val[i] : val[i + 7], 8, 64);
+                val[7] = 0.f;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) val[i] = (b4 ? val[i + 4] : val[i]) + __shfl_xor(b4 ? val[i] : val[i + 4], 4, 64);
+#pragma unroll
+                for (int i = 0; i < 2; ++i) val[i] = (b2 ? val[i + 2] : val[i]) + __shfl_xor(b2 ? val[i] : val[i + 2], 2, 64);
+                val[0] = (b1 ? val[1] : val[0]) + __shfl_xor(b1 ? val[0] : val[1], 1, 64);
+                const int rown = r4 + (own & (RG - 1));
+                const int ol = ob0 + (rown & 3) + 8 * (rown >> 2) + 4 * half;
+                if (own7 < 7 && n0 + ol < p.N) atomicAdd(&red[(own >> 2) * TN + ol], val[0]);
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {  // pass 2: stores only
+                const unsigned soff = (unsigned)(n0 + ob0 + (r & 3) + 8 * (r >> 2)) * plane_bytes;
+#pragma unroll
+                for (int pb = 0; pb < NPB; ++pb) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, gq[r][pb]), ry, yoff[pb], soff, 0);
+            }
+        }
+        __syncthreads();
+        if (tid < TN && n0 + tid < p.N) {
+            const int o = n0 + tid;
+            const int64_t bo = (int64_t)b * p.N + o;
+            atomicAdd(&p.dot_out[bo], red[tid]);
+            atomicAdd(&p.rgb_sums3[bo * 3 + 0], red[1 * TN + tid]);
+            atomicAdd(&p.rgb_sums3[bo * 3 + 1], red[2 * TN + tid]);
+            atomicAdd(&p.rgb_sums3[bo * 3 + 2], red[3 * TN + tid]);
+            const float u0 = red[4 * TN + tid], u1 = red[5 * TN + tid], u2 = red[6 * TN + tid];
+            if (styled) {
+                atomicAdd(&p.rgb_gw[bo], p.rgb_w[o] * u0 + p.rgb_w[p.N + o] * u1 + p.rgb_w[2 * p.N + o] * u2);
+            } else {
+                float* d = p.rgb_gw + (int64_t)b * 3 * p.N + o;
+                atomicAdd(d, u0), atomicAdd(d + p.N, u1), atomicAdd(d + 2 * p.N, u2);
+            }
+        }
+        return;
+    }
+
     // ---- epilogue
     // (EPI_ACT: the activation's gain sqrt(2) is folded into out_scale, bias and the noise strength -- lrelu(v)*g = lrelu(v*g), g > 0)
     const float nw = (EPI == EPI_ACT && p.noise) ? p.noise_w[0] * 1.4142135623730951f : 0.f;
@@ -1282,6 +1440,17 @@ static const TileCfg kCfgStd[] = {{2, 4, 2, 4}, {2, 4, 1, 8}, {1, 4, 1, 8},     
 static const int kNumCfg = 11;  // configurations of the per-phase / SAME / DOWN kernels
 static const int kNumCfgAll = 12;
 
+// What conv_impl decided for a launch, handed out instead of launching (`plan` argument): the entry points beside the dispatcher
+// (w2e_modconv_down_rgbfold) run the tile the cost model picks for the shape with an epilogue of their own.
+struct ConvPlan {
+    ConvParams p;
+    int cfg;
+    bool use_dma, use_x3;
+    size_t lds;
+    int64_t grid;
+    bool quiet;  // in: print nothing (a plan query); otherwise the layer line "modconv mode ..." is printed as for any conv launch
+};
+
 static int next_pow2(int v) {
     int r = 1;
     while (r < v) r <<= 1;
@@ -1309,9 +1478,9 @@ extern "C" int w2e_conv_pack(const float* weight, float* wp, int cout, int cin, 
 static int conv_impl(int mode, const float* x, const float* wp, const float* in_scale, const float* out_scale, float* y,
                      int batch, int k_ch, int n_ch, int h, int w, int act, const float* noise, const float* noise_w,
                      const float* bias, const float* dot_with, float* dot_out, const float* slope, int prelu, int down_pad,
-                     void* stream) {
+                     void* stream, ConvPlan* plan = nullptr) {
     W2E_REQUIRE(mode >= 0 && mode <= 2, "modconv3x3: bad mode %d", mode);
-    W2E_REQUIRE(x && wp && y, "modconv3x3: null tensor");
+    W2E_REQUIRE(plan || (x && wp && y), "modconv3x3: null tensor");
     W2E_REQUIRE(batch >= 0 && k_ch > 0 && n_ch > 0 && h > 0 && w > 0, "modconv3x3: bad dims");
     W2E_REQUIRE(!(act && mode != W2E_CONV_SAME), "modconv3x3: fused activation only in SAME mode");
     W2E_REQUIRE(!(prelu && (act || dot_with || mode == W2E_CONV_UP)), "conv3x3: the bias/PReLU epilogue is for SAME and DOWN, alone");
@@ -1465,7 +1634,8 @@ static int conv_impl(int mode, const float* x, const float* wp, const float* in_
         }
     }
     if (opt.deterministic) best_splits = 1;  // no fp32 atomics onto y: one workgroup owns every output element
-    if (opt.tune_print) fprintf(stderr, "modconv mode %d%s K %d N %d %dx%d B %d -> cfg %d splits %d\n", mode, use_all ? " (all-phase)" : "", k_ch, n_ch, h, w, batch, best, best_splits);
+    const bool print = opt.tune_print && !(plan && plan->quiet);
+    if (print) fprintf(stderr, "modconv mode %d%s K %d N %d %dx%d B %d -> cfg %d splits %d\n", mode, use_all ? " (all-phase)" : "", k_ch, n_ch, h, w, batch, best, best_splits);
     W2E_REQUIRE(best >= 0, "modconv3x3: no tile configuration for N=%d H=%d W=%d", n_ch, h, w);
     const TileCfg cfg = cfgs[best];
     W2E_REQUIRE(!use_all || cfg.npb >= 4, "modconv3x3: tile %d has no all-phase form (forced by tune_cfg)", best);  // (a forced tile: 0 pixel blocks per phase)
@@ -1498,7 +1668,7 @@ static int conv_impl(int mode, const float* x, const float* wp, const float* in_
         // (the pipeline addresses channels up to K+7 of an image with 32-bit byte offsets: they must not wrap)
         const bool off_ok = ((int64_t)k_ch + 8) * p.in_h * p.in_w * 4 < ((int64_t)1 << 32);
         if (off_ok && lds_dma <= 150 * 1024 && slots <= 4 * max_patch_slots(up ? W2E_CONV_UP : mode, tm, nt_best) + 1) use_dma = true, p.plane = plane16;
-        if (opt.tune_print) fprintf(stderr, "  lds-dma pipeline: %s (%zu B LDS, %d slots)\n", use_dma ? "yes" : "no", lds_dma, slots);
+        if (print) fprintf(stderr, "  lds-dma pipeline: %s (%zu B LDS, %d slots)\n", use_dma ? "yes" : "no", lds_dma, slots);
     }
     const int kdeep_best = (up && !use_all && cfg.nob * cfg.npb < 8 && max_patch_slots(mode, tm, nt_best) <= 2) ? 16 : kc;
     size_t lds = (up && !use_all) ? sizeof(float) * ((size_t)32 * tn + (size_t)kdeep_best * p.plane)
@@ -1528,14 +1698,14 @@ static int conv_impl(int mode, const float* x, const float* wp, const float* in_
         lds_dma = sizeof(float) * (((size_t)kc * 9 * tn + (size_t)kc * p.plane) + 4 * ((size_t)20 * tn + 2 * (size_t)p.plane) + (size_t)((k_ch + 7) / 8) * 8);
         use_x3 = lds_dma <= 160 * 1024;
         if (!use_x3 && mode == W2E_CONV_DOWN) use_dma = false;  // (DOWN takes the DMA pipeline only for this mode)
-        if (opt.tune_print) fprintf(stderr, "  bf16x3: %s (%zu B LDS)\n", use_x3 ? "yes" : "no", lds_dma);
+        if (print) fprintf(stderr, "  bf16x3: %s (%zu B LDS)\n", use_x3 ? "yes" : "no", lds_dma);
     }
     if (use_dma) lds = lds_dma;
     W2E_REQUIRE(lds <= 160 * 1024, "modconv3x3: tile needs %zu B of LDS", lds);
     const int k_gran = use_all ? kc : kc_max;
     p.k_per = (int)(ceil_div(ceil_div(k_ch, best_splits), k_gran) * k_gran);
     p.splits = (int)ceil_div(k_ch, p.k_per);
-    if (opt.tune_print) {  // the variant that runs (tests/test_gpu_conv_variants.py keys its coverage census on this line); a split
+    if (print && !plan) {  // the variant that runs (tests/test_gpu_conv_variants.py keys its coverage census on this line); a split
                            // activation / bias + PReLU runs as the plain kernel followed by an elementwise pass ("act_pass" / "prelu_pass")
         const char* epi = prelu ? (p.splits > 1 ? "prelu_pass" : "prelu") : act ? (p.splits > 1 ? "act_pass" : "act") : dot_with ? "dot" : "plain";
         fprintf(stderr, "modconv variant mode %d all %d cfg %d splits %d dma %d x3 %d epi %s\n", mode, use_all ? 1 : 0, best, p.splits,
@@ -1551,6 +1721,10 @@ static int conv_impl(int mode, const float* x, const float* wp, const float* in_
     }
     const int64_t grid = (int64_t)p.tiles_x * p.tiles_y * p.tiles_n * batch * ((up && !use_all) ? 4 : 1) * p.splits + p.border_wgs;
     W2E_REQUIRE(grid < ((int64_t)1 << 31), "modconv3x3: grid of %lld workgroups is too large", (long long)grid);  // (cast to int at every launch below)
+    if (plan) {  // the caller launches (or only asked)
+        plan->p = p, plan->cfg = best, plan->use_dma = use_dma, plan->use_x3 = use_x3, plan->lds = lds, plan->grid = grid;
+        return 0;
+    }
 #ifdef W2E_TUNING
     // tuning aid: W2E_TUNE_CLOCK=1 stamps every workgroup and reports the in-kernel shader clock (s_memtime ticks per
     // 100 MHz s_memrealtime tick) of every 64th launch -- the DVFS-limited clock is what an MFMA-bound kernel is priced by
@@ -1743,5 +1917,106 @@ extern "C" int w2e_modconv_upblur(const float* x, const float* wp, const float* 
     }
     launch_cfg<CONV_UPALL, EPI_PLAIN, 1, 8, 1, 8, 8, 1, 1>(p, (int)grid, lds, (hipStream_t)stream);
     W2E_LAUNCH_CHECK("modconv_upblur");
+    return 0;
+}
+
+// ---- the stride-2 dgrad conv of an up-sampling StyledConv with the ToRGB backward of the level it writes in its dot epilogue
+// (modconv_kernel<W2E_CONV_DOWN, EPI_DOT_RGB, ...>): the launch stores gpre instead of the input gradient, and the second pass
+// over x and that gradient (torgb_bwd_kernel<., true, true>) does not run.  The tile is the one conv_impl's cost model picks for the
+// shape (or tune_cfg forces); the epilogue exists for every DOWN tile that model can pick, in both pipelines where both exist.
+namespace w2e {
+
+static bool rgbfold_launch(const ConvPlan& pl, hipStream_t s) {
+    const ConvParams& p = pl.p;
+    const int grid = (int)pl.grid;
+    if (pl.use_dma) {
+        switch (pl.cfg) {
+            case 0: launch_cfg<W2E_CONV_DOWN, EPI_DOT_RGB, 2, 4, 2, 4, 8, 1>(p, grid, pl.lds, s); return true;
+            case 9: launch_cfg<W2E_CONV_DOWN, EPI_DOT_RGB, 2, 2, 2, 4, 8, 1>(p, grid, pl.lds, s); return true;
+            case 10: launch_cfg<W2E_CONV_DOWN, EPI_DOT_RGB, 2, 2, 1, 8, 8, 1>(p, grid, pl.lds, s); return true;
+        }
+        return false;
+    }
+    switch (pl.cfg) {  // (tiles 1, 2 and 8 stage more patch elements per thread than DOWN's register prefetch holds: never picked)
+        case 0: launch_cfg<W2E_CONV_DOWN, EPI_DOT_RGB, 2, 4, 2, 4, 8>(p, grid, pl.lds, s); return true;
+        case 3: launch_cfg<W2E_CONV_DOWN, EPI_DOT_RGB, 2, 2, 2, 2, 8>(p, grid, pl.lds, s); return true;
+        case 4: launch_cfg<W2E_CONV_DOWN, EPI_DOT_RGB, 1, 4, 2, 2, 8>(p, grid, pl.lds, s); return true;
+        case 5: launch_cfg<W2E_CONV_DOWN, EPI_DOT_RGB, 1, 2, 2, 2, 8>(p, grid, pl.lds, s); return true;
+        case 6: launch_cfg<W2E_CONV_DOWN, EPI_DOT_RGB, 1, 1, 2, 2, 8>(p, grid, pl.lds, s); return true;
+        case 7: launch_cfg<W2E_CONV_DOWN, EPI_DOT_RGB, 1, 1, 4, 1, 8>(p, grid, pl.lds, s); return true;
+        case 9: launch_cfg<W2E_CONV_DOWN, EPI_DOT_RGB, 2, 2, 2, 4, 8>(p, grid, pl.lds, s); return true;
+        case 10: launch_cfg<W2E_CONV_DOWN, EPI_DOT_RGB, 2, 2, 1, 8, 8>(p, grid, pl.lds, s); return true;
+    }
+    return false;
+}
+
+static bool rgbfold_has_cfg(bool dma, int cfg) {
+    return dma ? (cfg == 0 || cfg == 9 || cfg == 10) : (cfg == 0 || (cfg >= 3 && cfg <= 7) || cfg == 9 || cfg == 10);
+}
+
+// Why the folded form cannot take a launch the dispatcher planned, or nullptr.
+static const char* rgbfold_refusal(const Options& opt, const ConvPlan& pl) {
+    if (opt.deterministic) return "deterministic mode keeps the two-kernel path (the sums are joined with fp32 atomics)";
+    if (opt.conv_precision != 0 || pl.use_x3) return "conv_precision = bf16x3 keeps the two-kernel path";
+    if (pl.p.splits > 1) return "a split-K launch keeps the two-kernel path (the epilogue needs the complete sum)";
+    if (!rgbfold_has_cfg(pl.use_dma, pl.cfg)) return "the tile has no ToRGB-backward epilogue";
+    return nullptr;
+}
+
+// tune_rgbfold = -1: the levels where the folded launch measured faster than the pair (DOWN dot conv, torgb_bwd_actbwd) by more than
+// the spread of repeated runs (tools/layer_bench.py --rgbfold, profiles/rgbfold_layer_bench.txt, profiles/NOTES_rgbfold.md)
+static bool rgbfold_auto(const Options& opt, int batch, int k_ch, int n_ch, int h, int w) {
+    if (opt.tune_cfg >= 0 || opt.tune_dma >= 0) return false;  // a forced tile / pipeline is what the caller wants to see run
+    // measured at batch 4 and 8 (FFHQ-1024 shapes): the levels 128^2, 256^2 and 512^2 win at both (3.7 - 17.5 % of the pair, every folded
+    // run below every run of the pair); 64^2 wins by 3 % at batch 8 and lies inside the spread at batch 4; below, the dispatcher
+    // splits K and the form does not apply
+    (void)batch, (void)k_ch, (void)n_ch;
+    return (int64_t)h * w >= 128 * 128;
+}
+
+static int rgbfold_plan(int batch, int k_ch, int n_ch, int h, int w, bool quiet, ConvPlan* pl) {
+    pl->quiet = quiet;
+    // (the tile choice depends on the mode, the shape and the options alone: no tensor is looked at)
+    return conv_impl(W2E_CONV_DOWN, nullptr, nullptr, nullptr, nullptr, nullptr, batch, k_ch, n_ch, h, w, 0, nullptr, nullptr, nullptr, nullptr,
+                     nullptr, nullptr, 0, 0, nullptr, pl);
+}
+}  // namespace w2e
+
+extern "C" int w2e_modconv_down_rgbfold_plan(int batch, int k_ch, int n_ch, int h, int w, int* fold) {
+    W2E_REQUIRE(fold != nullptr, "modconv_down_rgbfold_plan: null argument");
+    const Options& opt = options();
+    *fold = 0;
+    if (opt.tune_rgbfold == 0 || batch <= 0 || k_ch <= 0 || n_ch <= 0 || h <= 0 || w <= 0) return 0;
+    if (opt.tune_rgbfold < 0 && !rgbfold_auto(opt, batch, k_ch, n_ch, h, w)) return 0;
+    ConvPlan pl{};
+    if (rgbfold_plan(batch, k_ch, n_ch, h, w, true, &pl) != 0) return 0;  // (e.g. a forced tile that does not fit: the caller's ordinary launch reports it)
+    *fold = rgbfold_refusal(opt, pl) ? 0 : 1;
+    return 0;
+}
+
+extern "C" int w2e_modconv_down_rgbfold(const float* x, const float* wp, const float* in_scale, const float* out_scale, float* gpre,
+                                        int batch, int k_ch, int n_ch, int h, int w, const float* dot_with, float* dot_out,
+                                        const float* gy, const float* wrgb, const float* style, const float* noise, float* sums3,
+                                        float* gw, float slope, float gain, void* stream) {
+    W2E_REQUIRE(x && wp && gpre && dot_with && dot_out && gy && wrgb && sums3 && gw, "modconv_down_rgbfold: null tensor");
+    W2E_REQUIRE(batch >= 0 && k_ch > 0 && n_ch > 0 && h > 0 && w > 0, "modconv_down_rgbfold: bad dims");
+    W2E_REQUIRE(gain > 0.f && slope > 0.f, "modconv_down_rgbfold: gain and slope must be positive");
+    if (batch == 0) return 0;
+    const Options& opt = options();
+    ConvPlan pl{};
+    const int rc = rgbfold_plan(batch, k_ch, n_ch, h, w, false, &pl);
+    if (rc != 0) return rc;
+    const char* why = rgbfold_refusal(opt, pl);
+    W2E_REQUIRE(!why, "modconv_down_rgbfold: %s (K %d N %d %dx%d B %d, cfg %d)", why, k_ch, n_ch, h, w, batch, pl.cfg);
+    W2E_REQUIRE((int64_t)3 * h * w * 4 < ((int64_t)1 << 31), "modconv_down_rgbfold: one image of the RGB gradient exceeds 2 GB");
+    ConvParams& p = pl.p;
+    p.x = x, p.wp = wp, p.in_scale = in_scale, p.out_scale = out_scale, p.y = gpre, p.dot_with = dot_with, p.dot_out = dot_out;
+    p.rgb_gy = gy, p.rgb_w = wrgb, p.rgb_style = style, p.rgb_noise = noise, p.rgb_sums3 = sums3, p.rgb_gw = gw;
+    p.rgb_slope = slope, p.rgb_gain = gain;
+    if (opt.tune_print)  // (a line of its own format after the layer line: the census of tests/test_gpu_rgbfold.py keys on it)
+        fprintf(stderr, "modconv rgbfold variant cfg %d dma %d styled %d noise %d K %d N %d %dx%d B %d\n", pl.cfg, pl.use_dma ? 1 : 0,
+                style ? 1 : 0, noise ? 1 : 0, k_ch, n_ch, h, w, batch);
+    W2E_REQUIRE(rgbfold_launch(pl, (hipStream_t)stream), "modconv_down_rgbfold: internal: configuration %d not instantiated", pl.cfg);
+    W2E_LAUNCH_CHECK("modconv_down_rgbfold");
     return 0;
 }

@@ -445,6 +445,36 @@ def _modconv_upblur_raw(x, wp, in_scale, out_scale, kernel, h, w, act):
     return y
 
 
+def _rgbfold_planned(b, k, n, h, w):
+    """Whether the library takes the stride-2 input-gradient conv of this shape with the ToRGB backward folded into its epilogue
+    (w2e_modconv_down_rgbfold_plan: option tune_rgbfold, the levels it measured faster on; never a split-K launch, deterministic mode,
+    bf16x3 or a tile without that epilogue)."""
+    fold = ctypes.c_int(0)
+    call("w2e_modconv_down_rgbfold_plan", b, k, n, h, w, ctypes.byref(fold))
+    return bool(fold.value)
+
+
+def _modconv_down_rgbfold_raw(g, wp, in_scale, out_scale, h, w, x, gy, wrgb, style, noise, out=None, dot_out=None, sums3=None, gw=None):
+    """One call of w2e_modconv_down_rgbfold (include/w2e.h K1f) -> (gpre, dot, sums3, gw).  g [b,k,2h+1,2w+1]; x [b,n,h,w]; gy [b,3,h,w];
+    wrgb [3,n] with style [b,n], or [b,3,n] with style None; noise [h*w] or None.  `out`, `dot_out`, `sums3`, `gw`: write into these
+    (the last three ZEROED: they are accumulated with atomics) instead of allocating."""
+    b, k = g.shape[0], g.shape[1]
+    n = wp.shape[3]
+    if wp.shape[0] != (k + 7) // 8:
+        raise RuntimeError(f"modconv: packed weight holds {wp.shape[0]} 8-channel groups, input has {k} channels")
+    dev = g.device
+    y = out if out is not None else torch.empty((b, n, h, w), device=dev, dtype=torch.float32)
+    dot = dot_out if dot_out is not None else torch.zeros((b, n), device=dev, dtype=torch.float32)
+    sums3 = sums3 if sums3 is not None else torch.zeros((b, n, 3), device=dev, dtype=torch.float32)
+    gw = gw if gw is not None else torch.zeros((b, n) if style is not None else (b, 3, n), device=dev, dtype=torch.float32)
+    sp = profiling.span("modconv3x3", 2.0 * b * k * n * 9 * h * w)
+    call("w2e_modconv_down_rgbfold", ptr(g), ptr(wp), ptr(in_scale), ptr(out_scale), ptr(y), b, k, n, h, w, ptr(x), ptr(dot), ptr(gy),
+         ptr(wrgb), ptr(style), ptr(noise), ptr(sums3), ptr(gw), 0.2, SQRT2, stream_ptr())
+    if sp is not None:
+        sp.end()
+    return y, dot, sums3, gw
+
+
 def _channel_dot(a, b, out=None):
     """[B,C] = sum_p a*b per plane (w2e_channel_sums: one wave per plane, fixed reduction order)."""
     n, c = a.shape[0], a.shape[1]
@@ -569,6 +599,44 @@ class ActLink:
         return sums
 
 
+class RgbFoldLink:
+    """Joins the three backward nodes around one pass-through ToRGB node of the synthesis loop, level R: the ToRGB node of level 2R,
+    whose backward produces that node's incoming RGB gradient (`gy`, recorded here); the up-sampling StyledConv of level 2R, whose
+    stride-2 input-gradient conv writes the tensor the ToRGB(R) backward would read, add to and rewrite; and ToRGB(R) itself, which
+    at forward time registers what its backward kernel would need (`saved`).  Autograd runs them in that order.  When the library
+    takes the shape (w2e_modconv_down_rgbfold_plan) the StyledConv backward runs the folded launch (w2e_modconv_down_rgbfold): what
+    it returns as its input gradient already IS the pre-activation gradient of the StyledConv below ToRGB(R), and it leaves that
+    tensor, its three sums and the ToRGB style / weight gradient here.  ToRGB(R)'s backward then runs no kernel for them -- if, and
+    only if, the two tensors it receives are those very tensors; the folded value cannot be un-folded, so anything else raises."""
+
+    __slots__ = ("gy", "saved", "gpre", "sums", "gw")
+
+    def __init__(self):
+        self.gy = self.saved = self.gpre = self.sums = self.gw = None
+
+    def usable(self, x, n_skip):
+        """(StyledConv backward) both neighbours have reported, for this very activation and the same no-grad prefix."""
+        if self.gy is None or self.saved is None:
+            return False
+        xs, _, _, _, ns = self.saved
+        return ns == n_skip and xs.shape[0] == x.shape[0] + n_skip and xs.data_ptr() + 4 * n_skip * xs[0].numel() == x.data_ptr() \
+            and tuple(xs.shape[1:]) == tuple(x.shape[1:]) and tuple(self.gy.shape) == (xs.shape[0], 3) + tuple(xs.shape[2:])
+
+    def take(self, gy, gx_next):
+        """(ToRGB backward) -> (gpre, sums, gw) of the folded launch, or None when it did not run."""
+        gpre, sums, gw, rec = self.gpre, self.sums, self.gw, self.gy
+        self.gpre = self.sums = self.gw = self.gy = None
+        if gpre is None:
+            return None
+        if gx_next is not gpre or gy is not rec:
+            raise RuntimeError("where2edit_amd: the ToRGB backward was folded into the stride-2 input-gradient conv of the level above "
+                               "(RgbFoldLink), but the gradients reached the ToRGB node as different tensors -- a tensor hook, "
+                               "retain_grad() or a second consumer on the passed-through activation or on the RGB skip image is not "
+                               "supported on the fused training path (use return_features=True / the unfused modules to tap "
+                               "activations, or the option tune_rgbfold = 0)")
+        return gpre, sums, gw
+
+
 class _StyledConv(torch.autograd.Function):
     """Fused StyledConv: out = lrelu(d * conv(Wp, s*x) [blur] + nw*noise + bias) * sqrt2 with
     d = rsqrt(s^2 @ wsq^T + eps) (model.py:234-276, 285-290, op/fused_act.py); with fuse_act=False just
@@ -579,9 +647,10 @@ class _StyledConv(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, s, wsq, noise, noise_w, bias, packs, blur_kernel, upsample, fuse_act, link=None, d_pre=None, weight=None,
-                wscale=1.0):
+                wscale=1.0, fold=None):
         """`d_pre`: the layer's demodulation vector when the caller already has it (demod_coefficients_all).  `weight`: the
-        trained raw conv weight (packs and wsq are then derived from it by the caller in this very forward)."""
+        trained raw conv weight (packs and wsq are then derived from it by the caller in this very forward).  `fold`: the RgbFoldLink
+        of the pass-through ToRGB node that x came through (up-sampling layers of the synthesis loop)."""
         x, s = _c(x), _c(s)
         b, cin, h, w = x.shape
         wp_f, wp_b = packs
@@ -605,6 +674,7 @@ class _StyledConv(torch.autograd.Function):
         ctx.cfg = (upsample, fuse_act)
         ctx.wscale = float(wscale)
         ctx.link = link  # (an ActLink shared with the consuming ToRGB node, or None)
+        ctx.fold = fold if (upsample and weight is None and d is not None) else None
         ctx.n_skip = _NOGRAD_PREFIX if _NOGRAD_PREFIX < b else 0
         ctx.pool = _GRAD_POOL
         return out
@@ -678,6 +748,18 @@ class _StyledConv(torch.autograd.Function):
             gx = _scale_planes(raw, s)
             if n_skip:
                 gx_out.copy_(gx)
+        elif ctx.fold is not None and ctx.fold.usable(x, n_skip) and _rgbfold_planned(b, gpre.shape[1], cin, h, w):
+            # x came through a ToRGB node whose backward would read x and this launch's output again: the launch does that node's work
+            # in its epilogue (RgbFoldLink) and what it writes is the pre-activation gradient of the StyledConv below that node
+            fold = ctx.fold
+            xr, wrgb, st, nz, _ = fold.saved
+            rgb_full = fold.gy.shape[0]
+            gw_full, gw = _zeros_with_tail(rgb_full, n_skip, (cin,) if st is not None else (3, cin), x.device, ctx.pool)
+            sums3 = ctx.pool.zeros((b, cin, 3), x.device) if ctx.pool is not None else None
+            gx, gs, sums3, _ = _modconv_down_rgbfold_raw(
+                gpre, wp_b, d, s, h, w, x, fold.gy[n_skip:] if n_skip else fold.gy, wrgb if (st is not None or not n_skip) else wrgb[n_skip:],
+                None if st is None else (st[n_skip:] if n_skip else st), nz, out=gx_out, dot_out=gs_out, sums3=sums3, gw=gw)
+            fold.gpre, fold.sums, fold.gw = (gx_full if n_skip else gx), sums3, gw_full
         else:
             gx, gs = _modconv_raw(mode, gpre, wp_b, d, s, h, w, dot_with=x, out=gx_out, dot_out=gs_out)
         if d is not None:  # + the demodulation path: gs -= s * (dz*d^2) @ wsq, with dz = sum_p gpre*(pre - nw*noise - bias)
@@ -685,11 +767,11 @@ class _StyledConv(torch.autograd.Function):
                  ptr(bias) if fuse_act else None, ptr(d), ptr(s), ptr(wsq), ptr(gs), None, b, cin, cout, stream_ptr())
         if n_skip:
             gx = gx_full
-        return gx, gs_full, None, None, g_nw, g_bias, None, None, None, None, None, None, g_w, None
+        return gx, gs_full, None, None, g_nw, g_bias, None, None, None, None, None, None, g_w, None, None
 
 
-def styled_conv(x, s, wsq, noise, noise_w, bias, packs, blur_kernel, upsample, link=None, demod=None, weight=None, wscale=1.0):
-    return _StyledConv.apply(x, s, wsq, noise, noise_w, bias, packs, blur_kernel, upsample, True, link, demod, weight, wscale)
+def styled_conv(x, s, wsq, noise, noise_w, bias, packs, blur_kernel, upsample, link=None, demod=None, weight=None, wscale=1.0, fold=None):
+    return _StyledConv.apply(x, s, wsq, noise, noise_w, bias, packs, blur_kernel, upsample, True, link, demod, weight, wscale, fold)
 
 
 def modconv(x, s, wsq, packs, blur_kernel, upsample, weight=None, wscale=1.0):
@@ -759,9 +841,11 @@ class _ToRGB(torch.autograd.Function):
     ToRGB input gradient by the kernel (w2e_torgb_bwd_acc) -- instead of autograd adding two activation-sized tensors."""
 
     @staticmethod
-    def forward(ctx, x, wmod, style, bias, skip, upk, passthrough=False, producer_act=None):
+    def forward(ctx, x, wmod, style, bias, skip, upk, passthrough=False, producer_act=None, fold_out=None, fold_skip=None):
         """`producer_act` = the ActLink of the fused StyledConv (slope 0.2, gain sqrt 2) whose output x is, when this node is its only
-        consumer (the pass-through form, or the last layer): the backward then returns that layer's PRE-activation gradient."""
+        consumer (the pass-through form, or the last layer): the backward then returns that layer's PRE-activation gradient.
+        `fold_out` / `fold_skip`: the RgbFoldLink of this node (pass-through form with `producer_act`) / of the ToRGB node `skip` came
+        from -- see there."""
         x_in = x
         x, wmod = _c(x), _c(wmod)
         b, cin, h, w = x.shape
@@ -779,8 +863,12 @@ class _ToRGB(torch.autograd.Function):
                  ptr(upk) if skip is not None else None, ptr(y), b, cin, h, w, stream_ptr())
         ctx.save_for_backward(x, wmod, style, upk if skip is not None else None, producer_act.noise if producer_act is not None else None)
         ctx.link = producer_act  # (the caller vouches that this node is x's only consumer)
-        ctx.has = (bias is not None, skip is not None, tuple(bias.shape) if bias is not None else None)
         ctx.n_skip = _NOGRAD_PREFIX if _NOGRAD_PREFIX < b else 0
+        ctx.fold_out = fold_out if (passthrough and producer_act is not None) else None
+        ctx.fold_skip = fold_skip if skip is not None else None
+        if ctx.fold_out is not None:  # what the backward kernel of this node would read, for the launch that does its work instead
+            ctx.fold_out.saved = (x.detach(), wmod.detach(), style.detach() if style is not None else None, producer_act.noise, ctx.n_skip)
+        ctx.has = (bias is not None, skip is not None, tuple(bias.shape) if bias is not None else None)
         ctx.pool = _GRAD_POOL
         if passthrough:
             return y, x_in.view_as(x_in)
@@ -794,8 +882,15 @@ class _ToRGB(torch.autograd.Function):
         n_skip = ctx.n_skip
         b, cin, h, w = x.shape
         if gy is None:  # only the pass-through output was used
-            return gx_next, None, None, None, None, None, None, None
+            return gx_next, None, None, None, None, None, None, None, None, None
+        folded = ctx.fold_out.take(gy, gx_next) if ctx.fold_out is not None else None
         gy = _c(gy)
+        if folded is not None:
+            # the stride-2 conv of the level above has done this node's kernel in its epilogue: gx_next IS the pre-activation gradient
+            gx, sums3, gw_full = folded
+            gys = gy[n_skip:] if n_skip else gy
+            ctx.link.gpre, ctx.link.sums = gx, sums3
+            return (gx,) + _rgb_small_grads(ctx, gys, gw_full, wmod, style, upk, n_skip, b, h, w, x.device)
         gx = _grad_rows(None, n_skip, x.device, like=x)
         acc = _c(gx_next) if gx_next is not None else None
         if n_skip:  # the tails of batch-major tensors: contiguous views, written / read in place
@@ -817,20 +912,29 @@ class _ToRGB(torch.autograd.Function):
         else:
             call("w2e_torgb_styled_bwd", ptr(xs), ptr(ws), ptr(sts), ptr(gys), ptr(accs), ptr(gxs), ptr(gw), b - n_skip, cin, h, w,
                  stream_ptr())
-        g_wmod, g_style = (gw_full.view_as(wmod), None) if style is None else (None, gw_full)
-        gb = gys.sum((0, 2, 3)).reshape(bias_shape) if (has_bias and ctx.needs_input_grad[3]) else None
-        gskip = None
-        if has_skip:  # adjoint of Upsample(up=2, pad=(2,1)): down=2, un-flipped taps, leading pad 4-1-2
-            gskip = _grad_rows((b, 3, h // 2, w // 2), n_skip, x.device)  # rows [:n_skip]: see _StyledConv
-            _upfirdn2d_raw(gys, upk, h // 2, w // 2, 1, 2, 1, 1, False, out=gskip[n_skip:] if n_skip else gskip)
-        return gx, g_wmod, g_style, gb, gskip, None, None, None
+        return (gx,) + _rgb_small_grads(ctx, gys, gw_full, wmod, style, upk, n_skip, b, h, w, x.device)
 
 
-def to_rgb(x, wmod, bias, skip, upk, passthrough=False, style=None, producer_act=None):
+def _rgb_small_grads(ctx, gys, gw_full, wmod, style, upk, n_skip, b, h, w, device):
+    """The tail of _ToRGB.backward's return tuple: weight or style gradient, the 3-channel bias gradient, and the gradient of the skip
+    image (recorded on the RgbFoldLink of the ToRGB node below, whose incoming gradient it is)."""
+    has_bias, has_skip, bias_shape = ctx.has
+    g_wmod, g_style = (gw_full.view_as(wmod), None) if style is None else (None, gw_full)
+    gb = gys.sum((0, 2, 3)).reshape(bias_shape) if (has_bias and ctx.needs_input_grad[3]) else None
+    gskip = None
+    if has_skip:  # adjoint of Upsample(up=2, pad=(2,1)): down=2, un-flipped taps, leading pad 4-1-2
+        gskip = _grad_rows((b, 3, h // 2, w // 2), n_skip, device)  # rows [:n_skip]: see _StyledConv
+        _upfirdn2d_raw(gys, upk, h // 2, w // 2, 1, 2, 1, 1, False, out=gskip[n_skip:] if n_skip else gskip)
+        if ctx.fold_skip is not None:
+            ctx.fold_skip.gy = gskip
+    return g_wmod, g_style, gb, gskip, None, None, None, None, None
+
+
+def to_rgb(x, wmod, bias, skip, upk, passthrough=False, style=None, producer_act=None, fold_out=None, fold_skip=None):
     """y = sum_i wmod[b,c,i] x[b,i] + bias + Upsample(skip)   (model.py:353-362); with `passthrough` -> (y, x).
     With `style` [B,cin]: wmod is the shared [3,cin] scale*W (treated as frozen) and the weight of sample b is
     wmod[c,i]*style[b,i]."""
-    return _ToRGB.apply(x, wmod, style, bias, skip, upk, passthrough, producer_act)
+    return _ToRGB.apply(x, wmod, style, bias, skip, upk, passthrough, producer_act, fold_out, fold_skip)
 
 
 # ------------------------------------------------------------------------------------------ K5

@@ -54,13 +54,13 @@ def span(name, work=0.0):
     return _Span(name, work) if (_active is not None and _active.enabled) else None
 
 
-SELECTION_PREFIXES = ("modconv mode", "modconv variant", "modconv upblur variant", "wino_fused variant", "upfirdn variant", "  ")
+SELECTION_PREFIXES = ("modconv mode", "modconv variant", "modconv upblur variant", "modconv rgbfold variant", "wino_fused variant", "upfirdn variant", "  ")
 
 
 def conv_selections(fn):
     """Runs fn() once with the library's `tune_print` option on and returns (lines, wino): `lines` = what w2e_modconv3x3 /
     w2e_conv3x3 / w2e_wino_fused / w2e_upfirdn2d / w2e_blur_adjoint_actbwd printed to stderr, in launch order ("modconv mode ..." with
-    its "  lds-dma ..." / "  bf16x3 ..." lines, "modconv variant ...", "modconv upblur variant ..." (w2e_modconv_upblur), "wino_fused variant ...", "upfirdn variant ..."), `wino` = the lines of the Winograd forms chosen on the Python side
+    its "  lds-dma ..." / "  bf16x3 ..." lines, "modconv variant ...", "modconv upblur variant ..." (w2e_modconv_upblur), "modconv rgbfold variant ..." (w2e_modconv_down_rgbfold), "wino_fused variant ...", "upfirdn variant ..."), `wino` = the lines of the Winograd forms chosen on the Python side
     (functional.WINO_LOG).  tools/cfg_selections.py and the coverage census in tests/test_gpu_conv_variants.py (conv and FIR variants) both use it."""
     from . import _lib
     from . import functional as K

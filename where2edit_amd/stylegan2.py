@@ -345,7 +345,9 @@ class StyledConv(nn.Module):
         self.noise = NoiseInjection()
         self.activate = FusedLeakyReLU(out_channel)
 
-    def forward(self, input, style, noise=None, input_is_stylespace=False, demod=None):
+    def forward(self, input, style, noise=None, input_is_stylespace=False, demod=None, fold=None):
+        """`fold` (synthesis loop, training, up-sampling layers): the functional.RgbFoldLink of the pass-through ToRGB node `input`
+        came through."""
         conv = self.conv
         batch = input.shape[0]
         fusable = (conv.kernel_size == 3 and not conv.downsample and noise is not None and noise.ndim == 4
@@ -365,7 +367,8 @@ class StyledConv(nn.Module):
         link = K.ActLink(noise_c) if (torch.is_grad_enabled() and not conv.upsample) else None
         out = K.styled_conv(input, s2d, wsq if conv.demodulate else None, noise_c, self.noise.weight, self.activate.bias, (fwd, bwd),
                             conv.blur.kernel if conv.upsample else None, conv.upsample, link=link,
-                            demod=demod if conv.demodulate else None, weight=conv.weight if train else None, wscale=conv.scale)
+                            demod=demod if conv.demodulate else None, weight=conv.weight if train else None, wscale=conv.scale,
+                            fold=fold if (conv.upsample and not train) else None)
         self._act_noise = link
         return out, style
 
@@ -384,10 +387,12 @@ class ToRGB(nn.Module):
         self.conv = ModulatedConv2d(in_channel, 3, 1, style_dim, demodulate=False)
         self.bias = nn.Parameter(torch.zeros(1, 3, 1, 1))
 
-    def forward(self, input, style, skip=None, input_is_stylespace=False, passthrough=False, producer_act=None):
+    def forward(self, input, style, skip=None, input_is_stylespace=False, passthrough=False, producer_act=None, fold_out=None,
+                fold_skip=None):
         """`passthrough` (synthesis loop, training): returns (rgb, style, input) -- see functional._ToRGB.  `producer_act`: the
         ActLink of the fused StyledConv whose output `input` is, when this ToRGB is its only consumer: the ToRGB backward then
-        applies that layer's activation backward to the gradient it returns (w2e_torgb_bwd_actbwd)."""
+        applies that layer's activation backward to the gradient it returns (w2e_torgb_bwd_actbwd).  `fold_out` / `fold_skip`: the
+        functional.RgbFoldLink of this node / of the ToRGB node `skip` came from (the fused skip form only)."""
         conv = self.conv
         batch = input.shape[0]
         style = conv._style(style, batch, input_is_stylespace)
@@ -407,10 +412,11 @@ class ToRGB(nn.Module):
         passed = None
         if passthrough:
             out, passed = K.to_rgb(input, wmod, self.bias, skip if fuse_skip else None, self.upsample.kernel if fuse_skip else None,
-                                   True, style=st, producer_act=None if _NO_RGBACT else producer_act)
+                                   True, style=st, producer_act=None if _NO_RGBACT else producer_act,
+                                   fold_out=None if _NO_RGBACT else fold_out, fold_skip=fold_skip if fuse_skip else None)
         else:
             out = K.to_rgb(input, wmod, self.bias, skip if fuse_skip else None, self.upsample.kernel if fuse_skip else None,
-                           style=st, producer_act=None if _NO_RGBACT else producer_act)
+                           style=st, producer_act=None if _NO_RGBACT else producer_act, fold_skip=fold_skip if fuse_skip else None)
         if skip is not None and not fuse_skip:
             out = out + self.upsample(skip)
         if passthrough:
@@ -555,11 +561,12 @@ class Generator(nn.Module):
         # the [B,C]-sized gradient accumulators of this pass's backward nodes come out of one zero-filled buffer (K.GradPool)
         batch = (latent[0] if input_is_stylespace else latent).shape[0]
         widths = sum(m.conv.in_channel for m, _, _, _ in self._layers())
-        with K.grad_pool(batch * (3 * widths + 64 * (len(self._layers()) + 2) + self.n_latent * self.style_dim)):
+        with K.grad_pool(batch * (3 * widths + 64 * (len(self._layers()) + 12) + self.n_latent * self.style_dim)):  # (+ the folded ToRGB backward's sums)
             return self._synthesis_pass(latent, noise, input_is_stylespace, on_layer, hook_layers)
 
     def _synthesis_pass(self, latent, noise, input_is_stylespace, on_layer, hook_layers):
         hook_all = on_layer
+        stylespace_in = input_is_stylespace
         batch_ref = latent[0] if input_is_stylespace else latent
         out = self.input(batch_ref)
         skip = None
@@ -578,6 +585,11 @@ class Generator(nn.Module):
             if idx:
                 demods = dict(zip(idx, K.demod_coefficients_all([batched[n] for n in idx], [plan[n][0].conv._derived()[2] for n in idx])))
         producer = None  # the fused-epilogue record of the StyledConv whose output `out` currently is
+        # the RgbFoldLink of the last pass-through ToRGB node: handed to the up-sampling conv that consumes the passed-through activation
+        # and to the next ToRGB node, which consumes the RGB image -- W+ latents, library option tune_rgbfold != 0
+        fold = None
+        fold_ok = (hook_all is None and not stylespace_in and torch.is_grad_enabled() and not _NO_RGBPASS and not _NO_RGBACT
+                   and out.is_cuda and K._lib.get_option("tune_rgbfold") != 0)
         for n, (mod, is_rgb, widx, nidx) in enumerate(plan):
             sty = latent[n] if input_is_stylespace else latent[:, widx]
             on_layer = hook_all if (hook_layers is None or n in hook_layers) else None
@@ -586,20 +598,27 @@ class Generator(nn.Module):
                 # (one consumer, the two gradients are joined inside torgb_bwd instead of by an elementwise add -- and the
                 # producing StyledConv's activation backward is applied there too)
                 if on_layer is None and n + 1 < len(plan) and torch.is_grad_enabled() and out.requires_grad and not _NO_RGBPASS:
-                    skip, s, out = mod(out, sty, skip, input_is_stylespace=input_is_stylespace, passthrough=True, producer_act=producer)
+                    link = K.RgbFoldLink() if (fold_ok and producer is not None) else None
+                    skip, s, out = mod(out, sty, skip, input_is_stylespace=input_is_stylespace, passthrough=True, producer_act=producer,
+                                       fold_out=link, fold_skip=fold)
+                    fold = link
                 elif on_layer is None and n + 1 == len(plan) and torch.is_grad_enabled() and out.requires_grad and not _NO_RGBPASS:
-                    skip, s = mod(out, sty, skip, input_is_stylespace=input_is_stylespace, producer_act=producer)  # (the last layer: sole consumer too)
+                    skip, s = mod(out, sty, skip, input_is_stylespace=input_is_stylespace, producer_act=producer, fold_skip=fold)  # (the last layer: sole consumer too)
+                    fold = None
                 else:
                     skip, s = mod(out, sty, skip, input_is_stylespace=input_is_stylespace)
+                    fold = None
                 if on_layer is not None:
                     skip = on_layer(n, True, skip)
                 producer = None
             else:
-                out, s = mod(out, sty, noise=noise[nidx], input_is_stylespace=input_is_stylespace, demod=demods.get(n))
+                out, s = mod(out, sty, noise=noise[nidx], input_is_stylespace=input_is_stylespace, demod=demods.get(n),
+                             fold=fold if mod.conv.upsample else None)
                 producer = getattr(mod, "_act_noise", None)
                 if on_layer is not None:
                     out = on_layer(n, False, out)
                     producer = None  # (the hook may have replaced the activation)
+                    fold = None
             style_vector.append(s)
         return skip, style_vector
 
