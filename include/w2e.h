@@ -44,6 +44,9 @@ extern "C" {
  * w2e_mask_iou_counts (w2e_attention.h, the mask IoU evaluation).
  * Still 7: w2e_modconv_upblur / w2e_modconv_upblur_plan and the option tune_upblur are additive too; so are
  * w2e_modconv_down_rgbfold / w2e_modconv_down_rgbfold_plan and the option tune_rgbfold */
+/* Still 7, although not additive: w2e_mapper_linear gained `gathered` and its mode 1 now reads the weight as stored (it took the
+ * transposed copy); w2e_mapper_gather and w2e_mapper_transpose are gone; w2e_ranger_step (K13, the optimizer update as one launch) is
+ * new.  The library and its one caller (where2edit_amd/) are built from the same tree, and the host tests pin the number. */
 #define W2E_VERSION 7
 
 int w2e_version(void);
@@ -373,19 +376,32 @@ int w2e_mask_blend_bwd(const float* gout, const float* a, const float* b, const 
  *   pixelnorm: h = x * rsqrt(mean over the level's latents of x^2 + 1e-8) per (sample, feature) (PixelNorm's dim=1 on a [B,L,512]
  *              slice, latent_mappers.py:16), x [batch, n_latent, 512], gathered into group-major rows.
  *   linear, mode 0: out = lrelu(w_scale * a W_g^T + b_scale * bias_g, 0.2) * sqrt2;  scatter != 0: out is [batch, n_latent, 512].
- *   linear, mode 1: out = w_scale * (a .* lrelu'(y_act)) W_g^T with W_g = the TRANSPOSED weight: the input gradient of a layer whose
- *                   output was y_act and output gradient a (both group-major).
+ *   linear, mode 1: out = w_scale * (a .* lrelu'(y_act)) W_g with W_g the weight AS STORED (no transposed copy): the input gradient
+ *                   of a layer whose output was y_act and output gradient a; gathered = 0: a and y_act are [batch, n_latent, 512]
+ *                   (the last layer), else group-major; out is group-major.  (`scatter` belongs to mode 0, `gathered` to mode 1.)
+ *                   Both modes sum in one fixed order without atomics: the same bits on every run.
  *   wgrad: gw_g = w_scale * gpre^T h_in, gb_g = b_scale * column sums of gpre, gpre = gy .* lrelu'(y); gathered = 0: gy and y are
- *          [batch, n_latent, 512] (the last layer), else group-major.  Fixed summation order (deterministic).
- *   gather: [batch, n_latent, 512] -> group-major rows.   transpose: wt[j] = w[j]^T for `count` <= 16 matrices. */
+ *          [batch, n_latent, 512] (the last layer), else group-major.  Fixed summation order (deterministic). */
 int w2e_mapper_pixelnorm(const float* x, float* h, int batch, int n_latent, int groups, const int* l0, const int* len, void* stream);
 int w2e_mapper_linear(int mode, const float* a, const float* y_act, float* out, const float* const* w, const float* const* bias,
                       int batch, int n_latent, int groups, const int* l0, const int* len, float w_scale, float b_scale, int scatter,
-                      void* stream);
+                      int gathered, void* stream);
 int w2e_mapper_wgrad(const float* gy, const float* y, const float* h_in, float* const* gw, float* const* gb, int batch, int n_latent,
                      int groups, const int* l0, const int* len, float w_scale, float b_scale, int gathered, void* stream);
-int w2e_mapper_gather(const float* src, float* dst, int batch, int n_latent, int groups, const int* l0, const int* len, void* stream);
-int w2e_mapper_transpose(const float* const* w, int count, float* wt, void* stream);
+
+/* ---- K13 (optimizer)  the Ranger update as one launch  (mapper/training/ranger.py:78-164: RAdam + look-ahead + gradient centralisation)
+ * `count` tensors by HOST arrays of device pointers (p, grad, exp_avg, exp_avg_sq, slow_buffer: contiguous fp32, numel[i] < 2^31
+ * elements each; a tensor of 0 elements is skipped) -- 64 tensors per launch, a further launch beyond that.  Per element, with
+ * g' = grad - (mean of grad over its row of row_len[i] elements, i.e. over all dimensions but the first) where row_len[i] > 0 and
+ * g' = grad where it is 0:
+ *   exp_avg_sq = beta2 * exp_avg_sq + (1 - beta2) * g'^2;   exp_avg = beta1 * exp_avg + (1 - beta1) * g';   p *= decay (if != 1);
+ *   p += neg_step_size * exp_avg / (sqrt(exp_avg_sq) + eps)  if rectified, else  p += neg_step_size * exp_avg;
+ *   lookahead != 0:  slow_buffer += alpha * (p - slow_buffer);  p = slow_buffer      (slow_buffer may be NULL otherwise).
+ * grad is only read.  The scalars are the host's finished values (neg_step_size = -step_size * lr, decay = 1 - weight_decay * lr), taken
+ * as doubles and rounded to fp32 once, 1 - beta included.  No atomics: the same bits on every run. */
+int w2e_ranger_step(int count, float* const* p, const float* const* grad, float* const* exp_avg, float* const* exp_avg_sq,
+                    float* const* slow_buffer, const int64_t* numel, const int64_t* row_len, double beta1, double beta2, double eps,
+                    double neg_step_size, int rectified, double decay, int lookahead, double alpha, void* stream);
 
 /* The style-space mappers (mapper/latent_mappers.py:84-128: FullStyleSpaceMapper / WithoutToRGBStyleSpaceMapper): `groups` (<= 32)
  * independent Mappers, Mapper c = PixelNorm over the dims[c] FEATURES of a [batch, dims[c]] code + 4 x EqualLinear(dims[c], dims[c],

@@ -12,6 +12,7 @@ _P = ctypes.c_void_p
 _I = ctypes.c_int
 _L = ctypes.c_int64
 _F = ctypes.c_float
+_D = ctypes.c_double
 
 class DemodLayer(ctypes.Structure):  # w2e_demod_layer (include/w2e.h)
     _fields_ = [("s", ctypes.c_void_p), ("wsq", ctypes.c_void_p), ("d", ctypes.c_void_p), ("cin", ctypes.c_int), ("cout", ctypes.c_int)]
@@ -25,10 +26,9 @@ _PROTOS = {
     "w2e_upfirdn2d": (_I, [_P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _F, _F, _P]),
     "w2e_blur_adjoint_actbwd": (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _F, _F, _P]),
     "w2e_mapper_pixelnorm": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
-    "w2e_mapper_linear": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _F, _F, _I, _P]),
+    "w2e_mapper_linear": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _F, _F, _I, _I, _P]),
     "w2e_mapper_wgrad": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _F, _F, _I, _P]),
-    "w2e_mapper_gather": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
-    "w2e_mapper_transpose": (_I, [_P, _I, _P, _P]),
+    "w2e_ranger_step": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _D, _D, _D, _D, _I, _D, _I, _D, _P]),
     "w2e_ssmapper_pixelnorm": (_I, [_P, _P, _I, _I, _P, _P]),
     "w2e_ssmapper_gather": (_I, [_P, _P, _I, _I, _P, _P]),
     "w2e_ssmapper_linear": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _F, _P]),

@@ -3,11 +3,13 @@
 // gradient and weight / bias gradients.  The products are [B*L, 512] x [512, 512] with B*L = 16..80 rows per level: far too small
 // for the matrix cores to matter (42 MFLOP per layer) and, as three rocBLAS calls + a bias/activation launch per layer and
 // direction, dominated by launch latency (about 120 launches per step).  Here a layer of ALL levels is one launch per direction:
-// fp32 FMA kernels, the level ("group") of a workgroup chosen by blockIdx.y.
+// fp32 FMA kernels, the level ("group") of a workgroup chosen by blockIdx.y (PixelNorm, weight gradient) or by the row tile that
+// blockIdx.y names (the two products of a layer, which split the rows of a level over workgroups to fill the chip).
 //
 // Activations live as [R, 512] with R = B*18 rows in group-major order: group g holds rows r0_g .. r0_g + B*L_g - 1, row
 // r0_g + b*L_g + l = latent l0_g + l of sample b.
 #include "common.h"
+#include "device.h"
 
 namespace w2e {
 
@@ -47,55 +49,135 @@ __global__ __launch_bounds__(256) void mapper_pixelnorm_kernel(const float* __re
     for (int l = 0; l < L; ++l) hp[(int64_t)l * MAP_D] = xp[(int64_t)l * MAP_D] * r;
 }
 
-// One EqualLinear of every group:  out[m, n] = epi( scale * sum_k a[m, k] * W_g[n, k] )   (rows m of group g, 16 columns n per
-// workgroup; W rows are staged in LDS, the rows of a are read as float4 through L1).
-//   MODE 0 (forward):        a = h_in,  epi(v) = lrelu(v + bias_g[n]*b_scale) * sqrt2                    (model.py:151-158)
-//   MODE 1 (input gradient): a = gy .* lrelu'(y)  (ACT_A: the activation backward of the layer's OUTPUT y applied to the operand
-//                            on the way),  W_g = the TRANSPOSED weight,  epi(v) = v
+// Both products of an EqualLinear run on a grid of (feature tile, row tile): a workgroup owns MAP_RT = 16 consecutive rows of ONE
+// group (blockIdx.y walks the row tiles of group 0, then of group 1, ...: 1 + 1 + 3 tiles at batch 4, 72 per group at MAP_MAXROWS
+// rows) and 8 features, so a layer of the step is 64 x 5 = 320 workgroups.  The 16 operand rows are staged in LDS once (rows past
+// the group's end as zeros), every weight element a thread needs is loaded into registers BEFORE the staging (16 independent
+// loads, nothing in the k loop waits on memory), and every sum has one fixed order: no atomics, the same bits on every run.
+constexpr int MAP_RT = 16;   // rows per workgroup
+constexpr int MAP_FT = 8;    // features per workgroup (outputs n in the forward, inputs i in the input gradient)
+
+struct MapTile {
+    int grp, m0, rows, r0;   // group, first row of the tile within the group, rows of the group, first row of the group
+};
+__device__ __forceinline__ MapTile map_tile(const MapGroups& g, int batch, int tile) {
+    MapTile t{0, 0, 0, 0};
+    for (int i = 0; i < g.groups; ++i) {
+        const int rows = g.len[i] * batch, tiles = (rows + MAP_RT - 1) / MAP_RT;
+        t.grp = i, t.rows = rows;
+        if (tile < tiles || i == g.groups - 1) break;
+        tile -= tiles, t.r0 += rows;
+    }
+    t.m0 = tile * MAP_RT;
+    return t;
+}
+// row m of group t.grp in a [B, n_latent, 512] tensor (`grouped` = 0) or in group-major rows
+__device__ __forceinline__ int64_t map_row_offset(const MapGroups& g, const MapTile& t, int m, int n_latent, int grouped) {
+    if (grouped) return (int64_t)(t.r0 + m) * MAP_D;
+    const int L = g.len[t.grp], b = m / L, l = m - b * L;
+    return ((int64_t)b * n_latent + g.l0[t.grp] + l) * MAP_D;
+}
+
+// Forward:  out[m, n] = lrelu(w_scale * sum_k a[m, k] W_g[n, k] + b_scale * bias_g[n]) * sqrt2              (model.py:151-158)
+// A wave owns two output features: its lanes split k (lane holds k = 4*lane .. +3 and 256 + 4*lane .. +3 of both weight rows: coalesced
+// b128 reads), the 16 rows accumulate in registers, 32 butterflies finish them and lane 16*q + m writes (row m, feature q).
 //   `scatter`: write row r0_g + b*L + l to out[b, l0_g + l, :] of a [B, n_latent, 512] tensor instead (the last forward layer).
-constexpr int MAP_TN = 16, MAP_PITCH = MAP_D + 4;
-template <int MODE>
-__global__ __launch_bounds__(256) void mapper_linear_kernel(const float* __restrict__ a, const float* __restrict__ y_act, float* __restrict__ out,
-                                                           MapGroups g, int batch, int n_latent, float w_scale, float b_scale, int scatter) {
-    __shared__ __attribute__((aligned(16))) float wt[MAP_TN * MAP_PITCH];
-    const int grp = blockIdx.y, n0 = blockIdx.x * MAP_TN, tid = threadIdx.x;
-    const float* W = g.w[grp];
-    for (int i = tid; i < MAP_TN * (MAP_D / 4); i += 256) {  // 16 weight rows, float4 at a time
-        const int n = i / (MAP_D / 4), q = i - n * (MAP_D / 4);
-        *reinterpret_cast<float4*>(wt + n * MAP_PITCH + 4 * q) = *reinterpret_cast<const float4*>(W + (int64_t)(n0 + n) * MAP_D + 4 * q);
+__global__ __launch_bounds__(256) void mapper_fwd_kernel(const float* __restrict__ a, float* __restrict__ out, MapGroups g, int batch, int n_latent,
+                                                        float w_scale, float b_scale, int scatter) {
+    __shared__ __attribute__((aligned(16))) float at[MAP_RT * MAP_D];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const MapTile t = map_tile(g, batch, blockIdx.y);
+    const int n0 = blockIdx.x * MAP_FT + 2 * wave;
+    const float4* W = reinterpret_cast<const float4*>(g.w[t.grp] + (int64_t)n0 * MAP_D);
+    float4 w[2][2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) w[q][j] = W[q * (MAP_D / 4) + lane + 64 * j];
+    for (int i = tid; i < MAP_RT * (MAP_D / 4); i += 256) {
+        const int m = i / (MAP_D / 4), k4 = i - m * (MAP_D / 4);
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (t.m0 + m < t.rows) v = reinterpret_cast<const float4*>(a + (int64_t)(t.r0 + t.m0 + m) * MAP_D)[k4];
+        reinterpret_cast<float4*>(at)[i] = v;
     }
     __syncthreads();
-    const int L = g.len[grp], rows = L * batch, r0 = map_row0(g, grp, batch);
-    const int n = tid & (MAP_TN - 1);
-    const float bs = (MODE == 0 && g.bias[grp]) ? g.bias[grp][n0 + n] * b_scale : 0.f;
-    for (int m = tid / MAP_TN; m < rows; m += 256 / MAP_TN) {
-        const float4* ap = reinterpret_cast<const float4*>(a + (int64_t)(r0 + m) * MAP_D);
-        const float4* yp = MODE == 1 ? reinterpret_cast<const float4*>(y_act + (int64_t)(r0 + m) * MAP_D) : nullptr;
-        const float4* wp = reinterpret_cast<const float4*>(wt + n * MAP_PITCH);
-        float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f;
-#pragma unroll 4
-        for (int k = 0; k < MAP_D / 4; ++k) {
-            float4 av = ap[k];
-            if (MODE == 1) {
-                const float4 yv = yp[k];
-                av.x *= MAP_GAIN * (yv.x > 0.f ? 1.f : MAP_SLOPE), av.y *= MAP_GAIN * (yv.y > 0.f ? 1.f : MAP_SLOPE);
-                av.z *= MAP_GAIN * (yv.z > 0.f ? 1.f : MAP_SLOPE), av.w *= MAP_GAIN * (yv.w > 0.f ? 1.f : MAP_SLOPE);
-            }
-            const float4 wv = wp[k];
-            acc0 += av.x * wv.x, acc1 += av.y * wv.y, acc2 += av.z * wv.z, acc3 += av.w * wv.w;
-        }
-        float v = ((acc0 + acc1) + (acc2 + acc3)) * w_scale;
-        if (MODE == 0) {
-            v += bs;
-            v = (v > 0.f ? v : v * MAP_SLOPE) * MAP_GAIN;
-        }
-        if (scatter) {
-            const int b = m / L, l = m - b * L;
-            out[((int64_t)b * n_latent + g.l0[grp] + l) * MAP_D + n0 + n] = v;
-        } else {
-            out[(int64_t)(r0 + m) * MAP_D + n0 + n] = v;
+    float acc[2][MAP_RT];
+#pragma unroll
+    for (int m = 0; m < MAP_RT; ++m) {
+        const float4 a0 = reinterpret_cast<const float4*>(at + m * MAP_D)[lane], a1 = reinterpret_cast<const float4*>(at + m * MAP_D)[lane + 64];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            float s = a0.x * w[q][0].x;
+            s += a0.y * w[q][0].y, s += a0.z * w[q][0].z, s += a0.w * w[q][0].w;
+            s += a1.x * w[q][1].x, s += a1.y * w[q][1].y, s += a1.z * w[q][1].z, s += a1.w * w[q][1].w;
+            acc[q][m] = s;
         }
     }
+    float v = 0.f;
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+#pragma unroll
+        for (int m = 0; m < MAP_RT; ++m) {
+            const float s = wave_sum(acc[q][m]);
+            if (lane == q * MAP_RT + m) v = s;
+        }
+    const int q = lane / MAP_RT, m = t.m0 + (lane & (MAP_RT - 1));
+    if (lane >= 2 * MAP_RT || m >= t.rows) return;
+    const int n = n0 + q;
+    v *= w_scale;
+    if (g.bias[t.grp]) v += g.bias[t.grp][n] * b_scale;
+    v = (v > 0.f ? v : v * MAP_SLOPE) * MAP_GAIN;
+    out[map_row_offset(g, t, m, n_latent, !scatter) + n] = v;
+}
+
+// Input gradient:  gx[m, i] = w_scale * sum_o gpre[m, o] W_g[o, i],  gpre = gy .* lrelu'(y)  -- the weight AS STORED (row o = output
+// feature o), read down its columns.  gpre of the 16 rows is staged in LDS with the activation backward applied on the way; gy / y
+// may be the [B, n_latent, 512] tensors of the LAST layer (`gathered` = 0) or group-major.  Thread (c, s) = (tid & 7, tid >> 3) owns
+// input feature i0 + c and the 16 outputs o = 4s + 128j + e (j, e < 4); the 32 slices s of a feature are summed by three butterfly
+// steps inside the wave, then over the four waves in ascending order through LDS.
+__global__ __launch_bounds__(256) void mapper_dgrad_kernel(const float* __restrict__ gy, const float* __restrict__ y, float* __restrict__ gx, MapGroups g,
+                                                          int batch, int n_latent, float w_scale, int gathered) {
+    __shared__ __attribute__((aligned(16))) float gp[MAP_RT * MAP_D];
+    __shared__ float part[4][MAP_RT][MAP_FT];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c = tid & (MAP_FT - 1), s = tid / MAP_FT;
+    const MapTile t = map_tile(g, batch, blockIdx.y);
+    const int i0 = blockIdx.x * MAP_FT;
+    const float* W = g.w[t.grp] + i0 + c;
+    float w[4][4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) w[j][e] = W[(int64_t)(4 * s + 128 * j + e) * MAP_D];
+    for (int i = tid; i < MAP_RT * (MAP_D / 4); i += 256) {
+        const int m = i / (MAP_D / 4), k4 = i - m * (MAP_D / 4);
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (t.m0 + m < t.rows) {
+            const int64_t off = map_row_offset(g, t, t.m0 + m, n_latent, gathered);
+            const float4 gv = reinterpret_cast<const float4*>(gy + off)[k4], yv = reinterpret_cast<const float4*>(y + off)[k4];
+            v.x = gv.x * MAP_GAIN * (yv.x > 0.f ? 1.f : MAP_SLOPE), v.y = gv.y * MAP_GAIN * (yv.y > 0.f ? 1.f : MAP_SLOPE);
+            v.z = gv.z * MAP_GAIN * (yv.z > 0.f ? 1.f : MAP_SLOPE), v.w = gv.w * MAP_GAIN * (yv.w > 0.f ? 1.f : MAP_SLOPE);
+        }
+        reinterpret_cast<float4*>(gp)[i] = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int m = 0; m < MAP_RT; ++m) {
+        float acc = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float4 p = reinterpret_cast<const float4*>(gp + m * MAP_D)[s + 32 * j];
+            acc += p.x * w[j][0], acc += p.y * w[j][1], acc += p.z * w[j][2], acc += p.w * w[j][3];
+        }
+#pragma unroll
+        for (int off = MAP_FT; off < 64; off <<= 1) acc += __shfl_xor(acc, off, 64);
+        if (lane < MAP_FT) part[wave][m][lane] = acc;
+    }
+    __syncthreads();
+    if (tid >= MAP_RT * MAP_FT) return;
+    const int m = tid / MAP_FT;
+    if (t.m0 + m >= t.rows) return;
+    const float v = ((part[0][m][c] + part[1][m][c]) + part[2][m][c]) + part[3][m][c];
+    gx[(int64_t)(t.r0 + t.m0 + m) * MAP_D + i0 + c] = v * w_scale;
 }
 
 // Weight and bias gradients of one EqualLinear of every group:
@@ -144,33 +226,6 @@ __global__ __launch_bounds__(256) void mapper_wgrad_kernel(const float* __restri
     }
 }
 
-// gathered pre-activation operand for the LAST layer's input gradient: a[r0_g + b*L + l, :] = gy[b, l0_g + l, :] (the activation
-// backward itself is applied by mapper_linear_kernel<1> from y) -- and y likewise
-__global__ __launch_bounds__(256) void mapper_gather_kernel(const float* __restrict__ src, float* __restrict__ dst, MapGroups g, int batch, int n_latent) {
-    const int grp = blockIdx.y;
-    const int L = g.len[grp], rows = L * batch, r0 = map_row0(g, grp, batch);
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < rows * (MAP_D / 4); e += gridDim.x * 256) {
-        const int m = e / (MAP_D / 4), q = e - m * (MAP_D / 4);
-        const int b = m / L, l = m - b * L;
-        reinterpret_cast<float4*>(dst + (int64_t)(r0 + m) * MAP_D)[q] =
-            reinterpret_cast<const float4*>(src + ((int64_t)b * n_latent + g.l0[grp] + l) * MAP_D)[q];
-    }
-}
-
-// wt[j][k][n] = w_j[n][k] for the `count` 512x512 matrices given by pointer (32x32 tiles through LDS)
-struct MapPtrs {
-    const float* w[16];
-};
-__global__ __launch_bounds__(256) void mapper_transpose_kernel(MapPtrs ptrs, float* __restrict__ wt) {
-    __shared__ float tile[32][33];
-    const float* w = ptrs.w[blockIdx.z];
-    float* o = wt + (int64_t)blockIdx.z * MAP_D * MAP_D;
-    const int bx = blockIdx.x * 32, by = blockIdx.y * 32, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int i = ty; i < 32; i += 8) tile[i][tx] = w[(int64_t)(by + i) * MAP_D + bx + tx];
-    __syncthreads();
-    for (int i = ty; i < 32; i += 8) o[(int64_t)(bx + i) * MAP_D + by + tx] = tile[tx][i];
-}
-
 static bool fill_groups(MapGroups& g, int groups, const int* l0, const int* len, int batch, int n_latent) {
     if (groups < 1 || groups > MAP_MAXG || batch < 1) return false;
     int total = 0;
@@ -199,9 +254,15 @@ extern "C" int w2e_mapper_pixelnorm(const float* x, float* h, int batch, int n_l
     return 0;
 }
 
+static int map_tiles(const MapGroups& g, int batch) {
+    int tiles = 0;
+    for (int i = 0; i < g.groups; ++i) tiles += (g.len[i] * batch + MAP_RT - 1) / MAP_RT;
+    return tiles;
+}
+
 extern "C" int w2e_mapper_linear(int mode, const float* a, const float* y_act, float* out, const float* const* w,
                                  const float* const* bias, int batch, int n_latent, int groups, const int* l0, const int* len,
-                                 float w_scale, float b_scale, int scatter, void* stream) {
+                                 float w_scale, float b_scale, int scatter, int gathered, void* stream) {
     W2E_REQUIRE(a && out && w && l0 && len, "mapper_linear: null argument");
     W2E_REQUIRE(mode == 0 || (mode == 1 && y_act), "mapper_linear: mode 0 (forward) or 1 (input gradient, needs the layer output)");
     MapGroups g{};
@@ -211,9 +272,9 @@ extern "C" int w2e_mapper_linear(int mode, const float* a, const float* y_act, f
         g.w[i] = w[i], g.bias[i] = (mode == 0 && bias) ? bias[i] : nullptr;
     }
     W2E_REQUIRE(((uintptr_t)a & 15) == 0 && (!y_act || ((uintptr_t)y_act & 15) == 0), "mapper_linear: operands must be 16-byte aligned");
-    dim3 grid(MAP_D / MAP_TN, (unsigned)groups);
-    if (mode == 0) mapper_linear_kernel<0><<<grid, 256, 0, (hipStream_t)stream>>>(a, nullptr, out, g, batch, n_latent, w_scale, b_scale, scatter);
-    else mapper_linear_kernel<1><<<grid, 256, 0, (hipStream_t)stream>>>(a, y_act, out, g, batch, n_latent, w_scale, b_scale, scatter);
+    dim3 grid(MAP_D / MAP_FT, (unsigned)map_tiles(g, batch));
+    if (mode == 0) mapper_fwd_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(a, out, g, batch, n_latent, w_scale, b_scale, scatter);
+    else mapper_dgrad_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(a, y_act, out, g, batch, n_latent, w_scale, gathered);
     W2E_LAUNCH_CHECK("mapper_linear");
     return 0;
 }
@@ -234,30 +295,6 @@ extern "C" int w2e_mapper_wgrad(const float* gy, const float* y, const float* h_
     mapper_wgrad_kernel<<<grid, 256, sizeof(float) * (size_t)max_rows * MAP_WN, (hipStream_t)stream>>>(gy, y, h_in, g, batch, n_latent, w_scale,
                                                                                                        b_scale, gathered);
     W2E_LAUNCH_CHECK("mapper_wgrad");
-    return 0;
-}
-
-extern "C" int w2e_mapper_gather(const float* src, float* dst, int batch, int n_latent, int groups, const int* l0, const int* len,
-                                 void* stream) {
-    W2E_REQUIRE(src && dst && l0 && len, "mapper_gather: null argument");
-    MapGroups g{};
-    W2E_REQUIRE(fill_groups(g, groups, l0, len, batch, n_latent), "mapper_gather: bad groups");
-    dim3 grid(64, (unsigned)groups);
-    mapper_gather_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(src, dst, g, batch, n_latent);
-    W2E_LAUNCH_CHECK("mapper_gather");
-    return 0;
-}
-
-extern "C" int w2e_mapper_transpose(const float* const* w, int count, float* wt, void* stream) {
-    W2E_REQUIRE(w && wt && count >= 1 && count <= 16, "mapper_transpose: 1..16 matrices");
-    MapPtrs p{};
-    for (int i = 0; i < count; ++i) {
-        W2E_REQUIRE(w[i], "mapper_transpose: null matrix");
-        p.w[i] = w[i];
-    }
-    dim3 grid(MAP_D / 32, MAP_D / 32, (unsigned)count);
-    mapper_transpose_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(p, wt);
-    W2E_LAUNCH_CHECK("mapper_transpose");
     return 0;
 }
 

@@ -1,7 +1,8 @@
 """The latent mapper MLPs on libw2e.so (csrc/mapper.hip, K7): LevelsMapper's three Mappers (mapper/latent_mappers.py:10-82) as ONE
 autograd node -- PixelNorm + 4 EqualLinear layers of all levels, one launch per layer and direction, weight and bias gradients
 included (these are the parameters the step trains).  About 120 stock-op launches per step (rocBLAS GEMMs of 16-80 rows, bias /
-activation, PixelNorm, reductions) become 13."""
+activation, PixelNorm, reductions) become 12: PixelNorm, 4 forward, 4 weight-gradient and 3 input-gradient launches.  The input
+gradient reads the weights as stored and the last layer's [B, n_latent, 512] tensors in place: no transposed copy, no gather."""
 import ctypes
 
 import torch
@@ -43,7 +44,7 @@ class _LevelsMLP(torch.autograd.Function):
         for j in range(LAYERS):
             last = j == LAYERS - 1
             call("w2e_mapper_linear", 0, ptr(h[j]), None, ptr(out if last else h[j + 1]), _ptr_array(weights[j * g:(j + 1) * g]),
-                 _ptr_array(biases[j * g:(j + 1) * g]), b, n_latent, g, l0, ln, float(w_scale), float(b_scale), int(last), st)
+                 _ptr_array(biases[j * g:(j + 1) * g]), b, n_latent, g, l0, ln, float(w_scale), float(b_scale), int(last), 0, st)
         ctx.save_for_backward(out, *h, *weights)
         ctx.geom = (levels, w_scale, b_scale, b, n_latent)
         return out
@@ -62,24 +63,16 @@ class _LevelsMLP(torch.autograd.Function):
         st = stream_ptr()
         gw = torch.empty((LAYERS * g, DIM, DIM), device=dev, dtype=torch.float32)
         gb = torch.empty((LAYERS * g, DIM), device=dev, dtype=torch.float32)
-        # transposed weights of layers 1..3 (the input gradient of layer 0 is not needed)
-        wt = torch.empty(((LAYERS - 1) * g, DIM, DIM), device=dev, dtype=torch.float32)
-        call("w2e_mapper_transpose", _ptr_array(weights[g:]), (LAYERS - 1) * g, ptr(wt), st)
-        gy, y, gathered = gout, out, 0  # the last layer's output and its gradient are [B, n_latent, 512]
+        gy, y, gathered = gout, out, 0  # the last layer's output and its gradient are [B, n_latent, 512]: both kernels index them in place
         for j in range(LAYERS - 1, -1, -1):
             call("w2e_mapper_wgrad", ptr(gy), ptr(y), ptr(h[j]), _ptr_array([gw[j * g + i] for i in range(g)]),
                  _ptr_array([gb[j * g + i] for i in range(g)]), b, n_latent, g, l0, ln, float(w_scale), float(b_scale), gathered, st)
-            if j == 0:
+            if j == 0:  # the input gradient of layer 0 is not needed
                 break
-            if not gathered:  # group-major copies of the last layer's (gradient, output) for the input-gradient product
-                ga, ya = torch.empty((rows, DIM), device=dev, dtype=torch.float32), torch.empty((rows, DIM), device=dev, dtype=torch.float32)
-                call("w2e_mapper_gather", ptr(gy), ptr(ga), b, n_latent, g, l0, ln, st)
-                call("w2e_mapper_gather", ptr(y), ptr(ya), b, n_latent, g, l0, ln, st)
-                gy, y, gathered = ga, ya, 1
             gh = torch.empty((rows, DIM), device=dev, dtype=torch.float32)
-            call("w2e_mapper_linear", 1, ptr(gy), ptr(y), ptr(gh), _ptr_array([wt[(j - 1) * g + i] for i in range(g)]), None, b, n_latent, g, l0, ln,
-                 float(w_scale), 0.0, 0, st)
-            gy, y = gh, h[j]
+            call("w2e_mapper_linear", 1, ptr(gy), ptr(y), ptr(gh), _ptr_array(weights[j * g:(j + 1) * g]), None, b, n_latent, g, l0, ln,
+                 float(w_scale), 0.0, 0, gathered, st)
+            gy, y, gathered = gh, h[j], 1
         grads = [gw[i] for i in range(LAYERS * g)] + [gb[i] for i in range(LAYERS * g)]
         return (None, None, None, None, *grads)
 
