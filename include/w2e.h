@@ -46,7 +46,8 @@ extern "C" {
  * w2e_modconv_down_rgbfold / w2e_modconv_down_rgbfold_plan and the option tune_rgbfold */
 /* Still 7, although not additive: w2e_mapper_linear gained `gathered` and its mode 1 now reads the weight as stored (it took the
  * transposed copy); w2e_mapper_gather and w2e_mapper_transpose are gone; w2e_ranger_step (K13, the optimizer update as one launch) is
- * new.  The library and its one caller (where2edit_amd/) are built from the same tree, and the host tests pin the number. */
+ * new.  The library and its one caller (where2edit_amd/) are built from the same tree, and the host tests pin the number.
+ * Still 7, additive: w2e_adam_step (K13b) and w2e_rstyle_* (K12e, w2e_attention.h: the region-attention net's style branch). */
 #define W2E_VERSION 7
 
 int w2e_version(void);
@@ -402,6 +403,18 @@ int w2e_mapper_wgrad(const float* gy, const float* y, const float* h_in, float* 
 int w2e_ranger_step(int count, float* const* p, const float* const* grad, float* const* exp_avg, float* const* exp_avg_sq,
                     float* const* slow_buffer, const int64_t* numel, const int64_t* row_len, double beta1, double beta2, double eps,
                     double neg_step_size, int rectified, double decay, int lookahead, double alpha, void* stream);
+
+/* ---- K13b (optimizer)  torch.optim.Adam's update as one launch  (the optimizer of attention/run_attention.py:1051, :1419; no amsgrad,
+ * no maximize).  `count` tensors by HOST arrays of device pointers (p, grad, exp_avg, exp_avg_sq: contiguous fp32, numel[i] < 2^31
+ * elements each; a tensor of 0 elements is skipped) -- 64 tensors per launch, a further launch beyond that.  Per element, with
+ * g' = grad + weight_decay * p:
+ *   exp_avg = beta1 * exp_avg + (1 - beta1) * g';   exp_avg_sq = beta2 * exp_avg_sq + (1 - beta2) * g'^2;
+ *   p -= step_size * exp_avg / (sqrt(exp_avg_sq) / bias_correction2_sqrt + eps)
+ * grad is only read.  The scalars are the host's finished values (step_size = lr / (1 - beta1^step), bias_correction2_sqrt =
+ * sqrt(1 - beta2^step) > 0), taken as doubles and rounded to fp32 once, 1 - beta included.  No atomics: the same bits on every run. */
+int w2e_adam_step(int count, float* const* p, const float* const* grad, float* const* exp_avg, float* const* exp_avg_sq,
+                  const int64_t* numel, double beta1, double beta2, double eps, double step_size, double bias_correction2_sqrt,
+                  double weight_decay, void* stream);
 
 /* The style-space mappers (mapper/latent_mappers.py:84-128: FullStyleSpaceMapper / WithoutToRGBStyleSpaceMapper): `groups` (<= 32)
  * independent Mappers, Mapper c = PixelNorm over the dims[c] FEATURES of a [batch, dims[c]] code + 4 x EqualLinear(dims[c], dims[c],

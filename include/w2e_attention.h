@@ -157,6 +157,43 @@ int w2e_cluster_pool_bwd(const float* g_final, const float* each, const float* s
 int w2e_mask_iou_counts(const float* mask, const uint8_t* label, const uint8_t* lut, float threshold, int batch, int classes,
                         int size, unsigned long long* counts, void* stream);
 
+/* ---- K12e: the style branch of FullSpaceMapperFEATClusterLinStyle_Net (attention/run_attention.py:811-828; csrc/region_style.hip) ----
+ * A grouped, rectangular EqualLinear family: `groups` (<= 32) independent layers on `batch` (<= 16) rows, one launch per direction.
+ * Group c maps one or two row-major sources -- src0[c] [batch, k0[c]] with row stride ld0[c], src1[c] [batch, k1[c]] with row stride
+ * ld1[c] (k1[c] = 0: no second source) -- contracted as if concatenated, through the weight AS STORED, w[c] [n[c], k0[c] + k1[c]]
+ * (model.py:130-164: row o = output feature o).  Everything per group goes by HOST arrays (device pointers, dimensions, w_scale[c] =
+ * that layer's EqualLinear scale, act[c] = 0 none / 1 fused LeakyReLU, slope 0.2, gain sqrt 2), so groups of one launch may come from
+ * different module families (mapper_c and mapper_text_c[0], :811 / :814), share a source (x_text) or point into packed buffers.
+ * k0 >= 1, k1 >= 0, n >= 1, k0 + k1 and n at most 4096; every width has a tail path (16-byte accesses where all widths and strides of
+ * a launch are multiples of 4 and all pointers 16-byte aligned).  b_scale = lr_mul.  fp32 FMA, fixed summation order, no atomics.
+ *   rstyle_linear_fwd    out[c][m, o] = act(w_scale * sum_k a[m, k] W[o, k] + b_scale * bias[c][o])    (bias, or bias[c], may be NULL)
+ *   rstyle_linear_dgrad  gx[m, i] = w_scale * sum_o gpre[m, o] W[o, i],  gpre = gy .* act'(y)  (y[c] = the layer's output; unread
+ *                        where act[c] = 0); columns i < k0 go to gx0[c] [batch, k0], the others to gx1[c] [batch, k1]; a NULL entry is
+ *                        a gradient nobody needs and is not computed (not both).  gpre is staged in LDS: batch * max n + 256 * MB <= 16384
+ *                        floats, MB = batch rounded up to a power of two.
+ *   rstyle_linear_wgrad  gw[c] = w_scale * gpre^T a  [n, k0 + k1],  gb[c] = b_scale * column sums of gpre (gb, or gb[c], may be NULL);
+ *                        WRITTEN, not accumulated.
+ * The finish (:820-821), per code c of width dims[c]; x[c] [batch, dims[c]] is read in place with row stride ldx[c]:
+ *   rstyle_finish_fwd    diff = alpha * (y - x);  x_new[c] = x + diff;  norms[c * batch + m] = ||diff[m, :]||_2;
+ *                        loss_delta[0] = sum_c mean_m norms[c, m] / layers     (two kernels; norms: groups * batch floats)
+ *   rstyle_finish_bwd    gy[c][m, j] = alpha * (g_out[c][m, j] + g_loss[0] * diff[m, j] / norms[c, m] / (batch * layers)); a row with
+ *                        norms == 0 takes 0 from the norm term (as torch's norm backward does; never NaN).  g_out[c] NULL = zeros;
+ *                        g_loss (a device scalar) NULL = 0. */
+int w2e_rstyle_linear_fwd(int groups, int batch, const float* const* src0, const float* const* src1, const int* k0, const int* k1,
+                          const int* ld0, const int* ld1, const float* const* w, const float* const* bias, float* const* out,
+                          const int* n, const float* w_scale, float b_scale, const int* act, void* stream);
+int w2e_rstyle_linear_dgrad(int groups, int batch, const float* const* gy, const float* const* y, const float* const* w,
+                            float* const* gx0, float* const* gx1, const int* k0, const int* k1, const int* n, const float* w_scale,
+                            const int* act, void* stream);
+int w2e_rstyle_linear_wgrad(int groups, int batch, const float* const* gy, const float* const* y, const float* const* src0,
+                            const float* const* src1, const int* k0, const int* k1, const int* ld0, const int* ld1, float* const* gw,
+                            float* const* gb, const int* n, const float* w_scale, float b_scale, const int* act, void* stream);
+int w2e_rstyle_finish_fwd(int groups, int batch, const float* const* x, const int* ldx, const float* const* y, float* const* x_new,
+                          const int* dims, float alpha, int layers, float* norms, float* loss_delta, void* stream);
+int w2e_rstyle_finish_bwd(int groups, int batch, const float* const* x, const int* ldx, const float* const* y,
+                          const float* const* g_out, const float* norms, const float* g_loss, float* const* gy, const int* dims,
+                          float alpha, int layers, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,8 @@ Layout:
   id_loss.py, irse_hip.py                  criteria/id_loss.py surface + IR-SE50 on the conv engine
   perceptual_loss.py                       criteria/perceptual_loss.py surface: VGG16 relu2_2 MSE on the conv engine
   coach.py, ranger.py     the mapper training step (mapper/training/coach.py:70-92) + optimizer
+  run_attention.py, region_style_hip.py, adam.py   the region-attention net and its training step (attention/run_attention.py): the
+                          style branch as one node on csrc/region_style.hip, `Adam` = torch.optim.Adam's rule as one launch
   dist.py                 data-parallel step: shard latents, one RCCL all-reduce of mapper grads
   evaluation.py           the region mask's IoU against parsing labels (utils.py:639-726): MaskIoU, calculate_iou
 """
@@ -57,6 +59,9 @@ _EVALUATION = ("CELEBAMASK_REGIONS", "region_lut", "binarise", "attention_with_t
 
 
 def __getattr__(name):
+    if name == "Adam":  # torch.optim.Adam's rule and state, the update as one launch (adam.py)
+        from .adam import Adam
+        return Adam
     if name in _EVALUATION:
         from . import evaluation
         return getattr(evaluation, name)

@@ -29,6 +29,7 @@ _PROTOS = {
     "w2e_mapper_linear": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _F, _F, _I, _I, _P]),
     "w2e_mapper_wgrad": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _F, _F, _I, _P]),
     "w2e_ranger_step": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _D, _D, _D, _D, _I, _D, _I, _D, _P]),
+    "w2e_adam_step": (_I, [_I, _P, _P, _P, _P, _P, _D, _D, _D, _D, _D, _D, _P]),
     "w2e_ssmapper_pixelnorm": (_I, [_P, _P, _I, _I, _P, _P]),
     "w2e_ssmapper_gather": (_I, [_P, _P, _I, _I, _P, _P]),
     "w2e_ssmapper_linear": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _F, _P]),

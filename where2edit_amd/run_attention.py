@@ -21,8 +21,9 @@ By default the mask branch is forward-only: the reference keeps every `attention
 module raises instead of silently returning a constant mask.  `train_mask_branch(net)` opts in to the differentiable
 branch (the same forward kernels inside autograd Functions whose backward is `w2e_cluster_pool_bwd` +
 `w2e_attention_logits_bwd`), and `RegionAttentionTrainer(train_mask_from=T)` is the reference's literal as a parameter.
-The style branch (`mapper_*`) is [B,1,C]-sized GEMMs on rocBLAS through torch + the fused bias/LeakyReLU op, fully
-differentiable."""
+The style branch (`mapper_*`) is one autograd node on the grouped EqualLinear kernels of csrc/region_style.hip
+(region_style_hip.py; differentiable in its parameters), with the stock composition -- [B,1,C]-sized GEMMs on rocBLAS through torch
++ the fused bias/LeakyReLU op, fully differentiable -- wherever the node does not apply."""
 import ctypes
 
 import torch
@@ -64,6 +65,12 @@ PROTOS = {
     "w2e_kmeans_pass": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_int64, ctypes.c_void_p] + [ctypes.c_int] * 6 +
                         [ctypes.c_void_p]),
     "w2e_kmeans_reduce": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    # the style branch (csrc/region_style.hip; host: region_style_hip.py)
+    "w2e_rstyle_linear_fwd": (ctypes.c_int, [ctypes.c_int] * 2 + [ctypes.c_void_p] * 11 + [ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]),
+    "w2e_rstyle_linear_dgrad": (ctypes.c_int, [ctypes.c_int] * 2 + [ctypes.c_void_p] * 11),
+    "w2e_rstyle_linear_wgrad": (ctypes.c_int, [ctypes.c_int] * 2 + [ctypes.c_void_p] * 12 + [ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]),
+    "w2e_rstyle_finish_fwd": (ctypes.c_int, [ctypes.c_int] * 2 + [ctypes.c_void_p] * 5 + [ctypes.c_float, ctypes.c_int] + [ctypes.c_void_p] * 3),
+    "w2e_rstyle_finish_bwd": (ctypes.c_int, [ctypes.c_int] * 2 + [ctypes.c_void_p] * 8 + [ctypes.c_float, ctypes.c_int, ctypes.c_void_p]),
 }
 
 
@@ -454,7 +461,14 @@ class FullSpaceMapperFEATClusterLinStyle_Net(nn.Module):
     # ---- the style branch (:806-822) ----------------------------------------------------------------------------------
     def new_styles(self, x, x_text, strength_alpha=0.1):
         """`strength_alpha`: the 0.1 of :820; the demo's copy of this net takes it as an argument
-        (show_demo/utils_demo.py:30: x_c + strength_alpha * (mapper_all(...) - x_c))."""
+        (show_demo/utils_demo.py:30: x_c + strength_alpha * (mapper_all(...) - x_c)).  Where region_style_hip.applies (CUDA fp32 codes
+        that need no gradient, B <= 16, at most 32 mapped codes, the reference's module structure; `W2E_RSTYLE_STOCK=1` forces the stock
+        composition) the whole branch is one autograd node on the w2e_rstyle_* kernels; otherwise the stock modules below."""
+        if x and torch.is_tensor(x[0]) and x[0].is_cuda:
+            from . import region_style_hip
+            res = region_style_hip.new_styles(self, x, x_text, strength_alpha)
+            if res is not None:
+                return res
         out = []
         loss_delta = 0
         for c in range(len(x)):
@@ -589,7 +603,8 @@ class RegionAttentionTrainer:
             self.params = [p for p in self.mapper.parameters() if p.requires_grad]
         else:
             self.params = list(self.mapper.parameters())
-        self.optimizer = torch.optim.Adam(self.params, lr=lr)
+        from .adam import Adam  # torch.optim.Adam's rule and state; the update is one launch (csrc/adam.hip)
+        self.optimizer = Adam(self.params, lr=lr)
         # `--amp` (run_attention.py:1068-1069, 1231, 1418-1421): the reference wraps the mapper + generator forward in autocast and drives
         # the optimizer through a GradScaler.  The kernels of this package compute in fp32 only, so there is nothing to autocast (a
         # narrower forward would also leave the north_star tolerance); what `amp=True` keeps is the GradScaler protocol -- the loss is
