@@ -47,7 +47,8 @@ extern "C" {
 /* Still 7, although not additive: w2e_mapper_linear gained `gathered` and its mode 1 now reads the weight as stored (it took the
  * transposed copy); w2e_mapper_gather and w2e_mapper_transpose are gone; w2e_ranger_step (K13, the optimizer update as one launch) is
  * new.  The library and its one caller (where2edit_amd/) are built from the same tree, and the host tests pin the number.
- * Still 7, additive: w2e_adam_step (K13b) and w2e_rstyle_* (K12e, w2e_attention.h: the region-attention net's style branch). */
+ * Still 7, additive: w2e_adam_step (K13b) and w2e_rstyle_* (K12e, w2e_attention.h: the region-attention net's style branch); and
+ * w2e_conv3x3_plan (the conv dispatcher's decision as a host-side query). */
 #define W2E_VERSION 7
 
 int w2e_version(void);
@@ -149,7 +150,16 @@ int w2e_modconv3x3(int mode, const float* x, const float* wp, const float* in_sc
                    float* y, int batch, int k_ch, int n_ch, int h, int w, int y_pitch, int act, const float* noise,
                    const float* noise_w, const float* bias, const float* dot_with, float* dot_out, void* stream);
 
-/* ---- K1u  the up-sampling StyledConv in ONE launch: W2E_CONV_UP with the 4x4 blur and the activation in the tile's epilogue -------
+/* What the dispatcher of w2e_modconv3x3 / w2e_conv3x3 would decide for a launch, after the library's current options (host code, no
+ * GPU: the decision looks at the mode, the shape and the options, never at a tensor).  prelu: 1 = w2e_conv3x3 with bias / slope;
+ * down_pad as for w2e_conv3x3.  out[W2E_CONV_PLAN_FIELDS] = use_all (UP: the all-phase form), cfg (tile), splits, k_per (channels per
+ * K split), use_dma, use_x3 (LDS-DMA pipeline / its bf16x3 form), lds (bytes), grid (workgroups; 0 for an empty batch), th, tw,
+ * tiles_x, tiles_y, tiles_n, plane (floats per staged channel), border_wgs (UP).  A shape the dispatcher refuses (a bad dimension, an
+ * image past 4 GB, a tile forced by "tune_cfg" that does not fit) returns non-zero with the launch's own w2e_last_error() text. */
+#define W2E_CONV_PLAN_FIELDS 15
+int w2e_conv3x3_plan(int mode, int batch, int k_ch, int n_ch, int h, int w, int prelu, int down_pad, int64_t* out);
+
+/* ---- K1u the up-sampling StyledConv in ONE launch: W2E_CONV_UP with the 4x4 blur and the activation in the tile's epilogue -------
  *     y[b,o] = lrelu(blur(out_scale[b,o] * conv_transpose(Wp, in_scale[b,i] * x[b,i])) + noise_w[0]*noise + bias[o], 0.2) * sqrt(2)
  * -- what w2e_modconv3x3(W2E_CONV_UP) followed by w2e_upfirdn2d(4x4, pad 1, flip = 1, in_layout = 1, act = 1, out_scale = NULL,
  * slope 0.2, gain sqrt 2) computes, to the summation order of the FIR; the (2H+1)x(2W+1) intermediate is never written.  kern: the

@@ -39,6 +39,7 @@ _PROTOS = {
     "w2e_bias_act_bwd_reduce": (_I, [_P, _P, _P, _P, _P, _L, _L, _L, _F, _F, _P]),
     "w2e_conv_pack": (_I, [_P, _P, _I, _I, _F, _I, _I, _P]),
     "w2e_modconv3x3": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "w2e_conv3x3_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int64)]),
     "w2e_modconv_upblur_plan": (_I, [_I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int)]),
     "w2e_modconv_upblur": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "w2e_modconv_down_rgbfold_plan": (_I, [_I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int)]),

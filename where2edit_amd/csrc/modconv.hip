@@ -28,6 +28,7 @@
 #include <string.h>
 
 #include <type_traits>
+#include <utility>
 
 #include "common.h"
 #include "../../include/w2e_irse.h"  // w2e_affine_act_fwd: the bias + PReLU pass after a split launch
@@ -1333,123 +1334,120 @@ struct TileCfg {
     int nob, npb, wo, wp;
 };
 
+// ---- the tile list: every tile's numbers, written once.  The cost model walks this list by index, the dispatcher (launch_tile) turns an
+// index into template arguments.
+constexpr TileCfg kCfgStd[] = {{2, 4, 2, 4}, {2, 4, 1, 8}, {1, 4, 1, 8},               // 512 threads, 1 workgroup / CU
+                               {2, 2, 2, 2}, {1, 4, 2, 2}, {1, 2, 2, 2}, {1, 1, 2, 2}, {1, 1, 4, 1}, {1, 4, 1, 4},  // 256 threads
+                               {2, 2, 2, 4}, {2, 2, 1, 8},  // 512 threads, 4 accumulators per wave (register headroom)
+                               {1, 8, 1, 8}};               // all-phase UP only: 32 channels x (4 phases x 2 pixel blocks)
+constexpr int kNumCfgAll = sizeof(kCfgStd) / sizeof(kCfgStd[0]);
+constexpr int kNumCfg = kNumCfgAll - 1;  // configurations of the per-phase / SAME / DOWN kernels
+
+// ---- the instantiation sets: which tiles modconv_kernel is built for, per mode / pipeline / epilogue, as bitmasks over the list.
+// They are what the library contains, not what it prefers (the measured preferences are in conv_plan, upblur_auto, rgbfold_auto).
+constexpr unsigned tiles() { return 0u; }
+template <class... R>
+constexpr unsigned tiles(int c, R... rest) {
+    return (1u << c) | tiles(rest...);
+}
+constexpr unsigned kRegStd = (1u << kNumCfg) - 1;        // register pipeline, SAME / DOWN
+constexpr unsigned kRegUp = (1u << kNumCfg) - 1;         // register pipeline, per-phase UP
+constexpr unsigned kRegUpAll = tiles(0, 1, 2, 4, 8, 11);  // all-phase UP (accumulator columns = 4 phases x NPB/4 pixel blocks)
+// The LDS-DMA pipeline is instantiated for the tiles the high-resolution layers use; other tiles keep the register pipeline.
+constexpr unsigned kDmaStd = tiles(0, 1, 2, 8, 9, 10);  // SAME / DOWN
+constexpr unsigned kDmaUpAll = tiles(0, 1, 2, 8, 11);
+// opt-in bf16x3 form (W2E_CONV_PRECISION=bf16x3), a variant of the DMA pipeline
+constexpr unsigned kX3Same = tiles(0, 1, 2, 8), kX3UpAll = tiles(0, 1, 2, 11), kX3Down = tiles(9);
+// the ToRGB-backward epilogue of DOWN (w2e_modconv_down_rgbfold): every DOWN tile the cost model can pick, in both pipelines where
+// both exist (tiles 1, 2 and 8 stage more patch elements per thread than DOWN's register prefetch holds: never picked)
+constexpr unsigned kRgbReg = tiles(0, 3, 4, 5, 6, 7, 9, 10), kRgbDma = tiles(0, 9, 10);
+
+// The tiles built for <MODE (CONV_UPALL = all-phase UP), EPI, DMA (0 register pipeline, 1 LDS-DMA, 2 bf16x3)>; 0 = no such kernel.
+constexpr unsigned tile_mask(int mode, int epi, int dma) {
+    const bool down = mode == W2E_CONV_DOWN;
+    if (epi == EPI_DOT_RGB) return !down || dma == 2 ? 0u : (dma ? kRgbDma : kRgbReg);
+    if (epi == EPI_PRELU) return is_up(mode) || dma ? 0u : kRegStd;  // (the bias/PReLU epilogue: fp32 register pipeline only)
+    if ((epi == EPI_ACT && mode != W2E_CONV_SAME) || (epi == EPI_DOT && is_up(mode))) return 0u;
+    if (mode == CONV_UPALL) return dma == 2 ? kX3UpAll : (dma ? kDmaUpAll : kRegUpAll);
+    if (mode == W2E_CONV_UP) return dma ? 0u : kRegUp;
+    return dma == 2 ? (down ? kX3Down : kX3Same) : (dma ? kDmaStd : kRegStd);
+}
+constexpr bool has_tile(unsigned mask, int cfg) { return cfg >= 0 && cfg < kNumCfgAll && ((mask >> cfg) & 1u) != 0; }
+
 template <int MODE, int EPI, int NOB, int NPB, int WO, int WP, int KC, int DMA = 0, int UPB = 0>
-static void launch_cfg(const ConvParams& p, int grid, size_t lds, hipStream_t s) {
+static int launch_cfg(const ConvParams& p, int grid, size_t lds, hipStream_t s) {
     if (lds > 64 * 1024) {  // dynamic LDS above 64 KB is opt-in per kernel and per device (gfx950: 160 KB per CU)
         static unsigned done = 0;
-        big_lds_once((const void*)modconv_kernel<MODE, EPI, NOB, NPB, WO, WP, KC, DMA, UPB>, &done);
+        W2E_REQUIRE(big_lds_once((const void*)modconv_kernel<MODE, EPI, NOB, NPB, WO, WP, KC, DMA, UPB>, &done),
+                    "modconv3x3: cannot enable %zu B of dynamic LDS for the kernel", lds);
     }
     modconv_kernel<MODE, EPI, NOB, NPB, WO, WP, KC, DMA, UPB><<<grid, 64 * WO * WP, lds, s>>>(p);
+    return 0;
 }
 
-// The LDS-DMA pipeline is instantiated for the tiles the high-resolution layers use; other tiles keep the register pipeline.
-static bool dma_has_cfg(bool all_phase, int cfg) {
-    return all_phase ? (cfg == 0 || cfg == 1 || cfg == 2 || cfg == 8 || cfg == 11)
-                     : (cfg == 0 || cfg == 1 || cfg == 2 || cfg == 8 || cfg == 9 || cfg == 10);
-}
-
-// opt-in bf16x3 form: the DOWN tile
-template <int EPI>
-static bool launch_x3_down(int cfg, const ConvParams& p, int grid, size_t lds, hipStream_t s) {
-    if (cfg != 9) return false;
-    launch_cfg<W2E_CONV_DOWN, EPI, 2, 2, 2, 4, 8, 2>(p, grid, lds, s);
-    return true;
-}
-
-// opt-in bf16x3 form: the all-phase UP tiles
-static bool launch_x3_up(int cfg, const ConvParams& p, int grid, size_t lds, hipStream_t s) {
-    switch (cfg) {
-        case 0: launch_cfg<CONV_UPALL, EPI_PLAIN, 2, 4, 2, 4, 8, 2>(p, grid, lds, s); return true;
-        case 1: launch_cfg<CONV_UPALL, EPI_PLAIN, 2, 4, 1, 8, 8, 2>(p, grid, lds, s); return true;
-        case 2: launch_cfg<CONV_UPALL, EPI_PLAIN, 1, 4, 1, 8, 8, 2>(p, grid, lds, s); return true;
-        case 11: launch_cfg<CONV_UPALL, EPI_PLAIN, 1, 8, 1, 8, 8, 2>(p, grid, lds, s); return true;
-    }
-    return false;
-}
-
-// opt-in bf16x3 form (W2E_CONV_PRECISION=bf16x3): the SAME-mode tiles of the DMA pipeline
-template <int EPI>
-static bool launch_x3(int cfg, const ConvParams& p, int grid, size_t lds, hipStream_t s) {
-    switch (cfg) {
-        case 0: launch_cfg<W2E_CONV_SAME, EPI, 2, 4, 2, 4, 8, 2>(p, grid, lds, s); return true;
-        case 1: launch_cfg<W2E_CONV_SAME, EPI, 2, 4, 1, 8, 8, 2>(p, grid, lds, s); return true;
-        case 2: launch_cfg<W2E_CONV_SAME, EPI, 1, 4, 1, 8, 8, 2>(p, grid, lds, s); return true;
-        case 8: launch_cfg<W2E_CONV_SAME, EPI, 1, 4, 1, 4, 8, 2>(p, grid, lds, s); return true;
-    }
-    return false;
-}
-
-template <int MODE, int EPI, int KC>
-static bool launch_mode_dma(int cfg, const ConvParams& p, int grid, size_t lds, hipStream_t s) {
-    if constexpr (MODE == CONV_UPALL) {
-        switch (cfg) {
-            case 0: launch_cfg<MODE, EPI, 2, 4, 2, 4, KC, 1>(p, grid, lds, s); return true;
-            case 1: launch_cfg<MODE, EPI, 2, 4, 1, 8, KC, 1>(p, grid, lds, s); return true;
-            case 2: launch_cfg<MODE, EPI, 1, 4, 1, 8, KC, 1>(p, grid, lds, s); return true;
-            case 8: launch_cfg<MODE, EPI, 1, 4, 1, 4, KC, 1>(p, grid, lds, s); return true;
-            case 11: launch_cfg<MODE, EPI, 1, 8, 1, 8, KC, 1>(p, grid, lds, s); return true;
-        }
-        return false;
+template <int MODE, int EPI, int DMA, bool BUILT, int I>
+static int launch_tile_i(const ConvParams& p, int grid, size_t lds, hipStream_t s) {
+    if constexpr (BUILT) {
+        constexpr TileCfg t = kCfgStd[I];
+        return launch_cfg<MODE, EPI, t.nob, t.npb, t.wo, t.wp, 8, DMA>(p, grid, lds, s);
     } else {
-        switch (cfg) {
-            case 0: launch_cfg<MODE, EPI, 2, 4, 2, 4, KC, 1>(p, grid, lds, s); return true;
-            case 1: launch_cfg<MODE, EPI, 2, 4, 1, 8, KC, 1>(p, grid, lds, s); return true;
-            case 2: launch_cfg<MODE, EPI, 1, 4, 1, 8, KC, 1>(p, grid, lds, s); return true;
-            case 8: launch_cfg<MODE, EPI, 1, 4, 1, 4, KC, 1>(p, grid, lds, s); return true;
-            case 9: launch_cfg<MODE, EPI, 2, 2, 2, 4, KC, 1>(p, grid, lds, s); return true;
-            case 10: launch_cfg<MODE, EPI, 2, 2, 1, 8, KC, 1>(p, grid, lds, s); return true;
-        }
-        return false;
+        return -1;
     }
 }
 
-template <int MODE, int EPI, int KC>
-static bool launch_mode(int cfg, const ConvParams& p, int grid, size_t lds, hipStream_t s) {
-    if constexpr (MODE == CONV_UPALL) {  // accumulator columns = 4 phases x NPB/4 pixel blocks
-        switch (cfg) {
-            case 0: launch_cfg<MODE, EPI, 2, 4, 2, 4, KC>(p, grid, lds, s); return true;
-            case 1: launch_cfg<MODE, EPI, 2, 4, 1, 8, KC>(p, grid, lds, s); return true;
-            case 2: launch_cfg<MODE, EPI, 1, 4, 1, 8, KC>(p, grid, lds, s); return true;
-            case 4: launch_cfg<MODE, EPI, 1, 4, 2, 2, KC>(p, grid, lds, s); return true;
-            case 8: launch_cfg<MODE, EPI, 1, 4, 1, 4, KC>(p, grid, lds, s); return true;
-            case 11: launch_cfg<MODE, EPI, 1, 8, 1, 8, KC>(p, grid, lds, s); return true;
-        }
-        return false;
-    } else {
-        switch (cfg) {
-            case 0: launch_cfg<MODE, EPI, 2, 4, 2, 4, KC>(p, grid, lds, s); return true;
-            case 1: launch_cfg<MODE, EPI, 2, 4, 1, 8, KC>(p, grid, lds, s); return true;
-            case 2: launch_cfg<MODE, EPI, 1, 4, 1, 8, KC>(p, grid, lds, s); return true;
-            case 3: launch_cfg<MODE, EPI, 2, 2, 2, 2, KC>(p, grid, lds, s); return true;
-            case 4: launch_cfg<MODE, EPI, 1, 4, 2, 2, KC>(p, grid, lds, s); return true;
-            case 5: launch_cfg<MODE, EPI, 1, 2, 2, 2, KC>(p, grid, lds, s); return true;
-            case 6: launch_cfg<MODE, EPI, 1, 1, 2, 2, KC>(p, grid, lds, s); return true;
-            case 7: launch_cfg<MODE, EPI, 1, 1, 4, 1, KC>(p, grid, lds, s); return true;
-            case 8: launch_cfg<MODE, EPI, 1, 4, 1, 4, KC>(p, grid, lds, s); return true;
-            case 9: launch_cfg<MODE, EPI, 2, 2, 2, 4, KC>(p, grid, lds, s); return true;
-            case 10: launch_cfg<MODE, EPI, 2, 2, 1, 8, KC>(p, grid, lds, s); return true;
-        }
-        return false;
-    }
+// The one dispatcher: tile index -> template arguments, for the tiles of MASK only.  A new tile or epilogue is one list entry and one
+// mask bit; a (mode, epilogue, pipeline) the planner can produce without a bit here ends in the error below.
+template <int MODE, int EPI, int DMA, unsigned MASK, int... I>
+static int launch_tile(int cfg, const ConvParams& p, int grid, size_t lds, hipStream_t s, std::integer_sequence<int, I...>) {
+    int rc = -1;
+    ((cfg == I ? (void)(rc = launch_tile_i<MODE, EPI, DMA, ((MASK >> I) & 1u) != 0, I>(p, grid, lds, s)) : (void)0), ...);
+    W2E_REQUIRE(rc >= 0, "modconv3x3: internal: configuration %d not instantiated", cfg);
+    return rc;
 }
 
-static const TileCfg kCfgStd[] = {{2, 4, 2, 4}, {2, 4, 1, 8}, {1, 4, 1, 8},               // 512 threads, 1 workgroup / CU
-                                   {2, 2, 2, 2}, {1, 4, 2, 2}, {1, 2, 2, 2}, {1, 1, 2, 2}, {1, 1, 4, 1}, {1, 4, 1, 4},  // 256 threads
-                                   {2, 2, 2, 4}, {2, 2, 1, 8},  // 512 threads, 4 accumulators per wave (register headroom)
-                                   {1, 8, 1, 8}};               // all-phase UP only: 32 channels x (4 phases x 2 pixel blocks)
-static const int kNumCfg = 11;  // configurations of the per-phase / SAME / DOWN kernels
-static const int kNumCfgAll = 12;
-
-// What conv_impl decided for a launch, handed out instead of launching (`plan` argument): the entry points beside the dispatcher
-// (w2e_modconv_down_rgbfold) run the tile the cost model picks for the shape with an epilogue of their own.
+// What conv_plan decided for a launch: the entry points print it (conv_print), add the tensors and launch it (conv_launch, or an
+// epilogue of their own: w2e_modconv_down_rgbfold), or only report it (w2e_conv3x3_plan).
 struct ConvPlan {
-    ConvParams p;
-    int cfg;
+    ConvParams p;  // the shape-dependent fields; no tensor
+    int mode;
+    bool use_all;         // UP: the all-phase form
+    int cfg, req_splits;  // req_splits: the split the cost model asked for (p.splits: after rounding the slices to whole K-chunks)
     bool use_dma, use_x3;
     size_t lds;
-    int64_t grid;
-    bool quiet;  // in: print nothing (a plan query); otherwise the layer line "modconv mode ..." is printed as for any conv launch
+    int64_t grid;  // 0: an empty batch, nothing to launch
+    // for the tune_print lines: whether the LDS-DMA pipeline / the bf16x3 form was considered, and with which numbers
+    bool dma_tried, dma_taken;
+    size_t dma_lds, x3_lds;
+    int dma_slots;
 };
+
+// runtime (mode, epilogue, pipeline) -> the dispatcher's template arguments
+template <int MODE, int EPI, int DMA>
+static int launch_variant(const ConvPlan& pl, const ConvParams& p, hipStream_t s) {
+    return launch_tile<MODE, EPI, DMA, tile_mask(MODE, EPI, DMA)>(pl.cfg, p, (int)pl.grid, pl.lds, s, std::make_integer_sequence<int, kNumCfgAll>{});
+}
+template <int MODE, int EPI>
+static int launch_pipeline(const ConvPlan& pl, const ConvParams& p, hipStream_t s) {
+    return pl.use_x3 ? launch_variant<MODE, EPI, 2>(pl, p, s) : pl.use_dma ? launch_variant<MODE, EPI, 1>(pl, p, s) : launch_variant<MODE, EPI, 0>(pl, p, s);
+}
+template <int MODE>
+static int launch_epilogue(const ConvPlan& pl, const ConvParams& p, int epi, hipStream_t s) {
+    switch (epi) {
+        case EPI_ACT: return launch_pipeline<MODE, EPI_ACT>(pl, p, s);
+        case EPI_DOT: return launch_pipeline<MODE, EPI_DOT>(pl, p, s);
+        case EPI_PRELU: return launch_pipeline<MODE, EPI_PRELU>(pl, p, s);
+        case EPI_DOT_RGB: return launch_pipeline<MODE, EPI_DOT_RGB>(pl, p, s);
+    }
+    return launch_pipeline<MODE, EPI_PLAIN>(pl, p, s);
+}
+static int launch_plan(const ConvPlan& pl, const ConvParams& p, int epi, hipStream_t s) {
+    if (pl.use_all) return launch_epilogue<CONV_UPALL>(pl, p, epi, s);
+    switch (pl.mode) {
+        case W2E_CONV_UP: return launch_epilogue<W2E_CONV_UP>(pl, p, epi, s);
+        case W2E_CONV_DOWN: return launch_epilogue<W2E_CONV_DOWN>(pl, p, epi, s);
+    }
+    return launch_epilogue<W2E_CONV_SAME>(pl, p, epi, s);
+}
 
 static int next_pow2(int v) {
     int r = 1;
@@ -1457,37 +1455,44 @@ static int next_pow2(int v) {
     return r;
 }
 
-}  // namespace w2e
-
-using namespace w2e;
-
-extern "C" int w2e_conv_pack(const float* weight, float* wp, int cout, int cin, float scale, int transpose, int flip,
-                             void* stream) {
-    W2E_REQUIRE(weight && wp, "conv_pack: null tensor");
-    W2E_REQUIRE(cout > 0 && cin > 0, "conv_pack: bad dims");
-    const int64_t total = (int64_t)(((transpose ? cout : cin) + 7) / 8) * 72 * (transpose ? cin : cout) * 4;
-    conv_pack_kernel<<<stream_grid(total, 256), 256, 0, (hipStream_t)stream>>>(weight, wp, cout, cin, scale, transpose,
-                                                                             flip);
-    W2E_LAUNCH_CHECK("conv_pack");
-    return 0;
+// Geometry of tile t (all_phase: its all-phase UP form) for an image `w` wide: tn output channels x tm pixels as th x tw, nt threads,
+// staged patch ph x pw.  (th = 0: the tile has no such form.)
+struct TileGeom {
+    int tn, tm, tw, th, nt, ph, pw;
+};
+static TileGeom tile_geom(int mode, bool all_phase, const TileCfg& t, int w) {
+    const int wp2 = next_pow2(w);
+    TileGeom g;
+    g.tn = 32 * t.nob * t.wo, g.tm = 32 * (all_phase ? t.npb / 4 : t.npb) * t.wp;
+    g.tw = wp2 < 32 ? wp2 : ((wp2 >= 64 && g.tm >= 256) ? 64 : 32);
+    g.th = g.tm / g.tw;
+    g.nt = 64 * t.wo * t.wp;
+    g.ph = mode == W2E_CONV_SAME ? g.th + 2 : (mode == W2E_CONV_UP ? g.th + 1 : 2 * g.th + 1);
+    g.pw = mode == W2E_CONV_SAME ? g.tw + 2 : (mode == W2E_CONV_UP ? g.tw + 1 : 2 * g.tw + 1);
+    return g;
 }
 
-// The engine behind w2e_modconv3x3 (StyleGAN2 layers) and w2e_conv3x3 (plain convolutions with folded BatchNorm / PReLU:
-// IR-SE50, the e4e encoder).  prelu: epilogue v = prelu(out_scale*acc + bias[o], slope[o]) (SAME / DOWN, no split-K);
-// down_pad: DOWN reads an (2h) x (2w) image with a one-pixel zero border on the top/left (stride 2, padding 1).
-static int conv_impl(int mode, const float* x, const float* wp, const float* in_scale, const float* out_scale, float* y,
-                     int batch, int k_ch, int n_ch, int h, int w, int act, const float* noise, const float* noise_w,
-                     const float* bias, const float* dot_with, float* dot_out, const float* slope, int prelu, int down_pad,
-                     void* stream, ConvPlan* plan = nullptr) {
+// Whether the LDS-DMA pipeline can stage the planned tile's patch (whole DMA wave-instructions, 16 pixels x 4 channels, per plane).
+static bool dma_fits(int mode, const ConvParams& p, const TileGeom& g, int* slots) {
+    const int plane16 = (p.plane + 15) & ~15;
+    *slots = (int)ceil_div(4 * plane16, g.nt);
+    // (the pipeline addresses channels up to K+7 of an image with 32-bit byte offsets: they must not wrap)
+    const bool off_ok = ((int64_t)p.K + 8) * p.in_h * p.in_w * 4 < ((int64_t)1 << 32);
+    return off_ok && *slots <= 4 * max_patch_slots(mode, g.tm, g.nt) + 1;
+}
+
+// The decision behind w2e_modconv3x3 (StyleGAN2 layers) and w2e_conv3x3 (plain convolutions with folded BatchNorm / PReLU: IR-SE50,
+// the e4e encoder): tile, split-K, pipeline, LDS and grid for one launch.  Pure host arithmetic on the mode, the shape and the
+// options: no tensor, no HIP call, no output (w2e_conv3x3_plan hands it out as it is).
+// prelu: epilogue v = prelu(out_scale*acc + bias[o], slope[o]) (SAME / DOWN, no split-K); down_pad: DOWN reads an (2h) x (2w) image
+// with a one-pixel zero border on the top/left (stride 2, padding 1).
+static int conv_plan(int mode, int batch, int k_ch, int n_ch, int h, int w, int prelu, int down_pad, const Options& opt, ConvPlan* pl) {
+    *pl = ConvPlan{};
     W2E_REQUIRE(mode >= 0 && mode <= 2, "modconv3x3: bad mode %d", mode);
-    W2E_REQUIRE(plan || (x && wp && y), "modconv3x3: null tensor");
     W2E_REQUIRE(batch >= 0 && k_ch > 0 && n_ch > 0 && h > 0 && w > 0, "modconv3x3: bad dims");
-    W2E_REQUIRE(!(act && mode != W2E_CONV_SAME), "modconv3x3: fused activation only in SAME mode");
-    W2E_REQUIRE(!(prelu && (act || dot_with || mode == W2E_CONV_UP)), "conv3x3: the bias/PReLU epilogue is for SAME and DOWN, alone");
+    W2E_REQUIRE(!(prelu && mode == W2E_CONV_UP), "conv3x3: the bias/PReLU epilogue is for SAME and DOWN, alone");
     W2E_REQUIRE(!(down_pad && mode != W2E_CONV_DOWN), "conv3x3: down_pad is a DOWN-mode option");
-    W2E_REQUIRE(!(dot_with && (act || mode == W2E_CONV_UP)), "modconv3x3: dot epilogue only without act, not in UP mode");
-    W2E_REQUIRE((dot_with == nullptr) == (dot_out == nullptr), "modconv3x3: dot_with and dot_out go together");
-    W2E_REQUIRE(!noise || noise_w, "modconv3x3: noise without noise_w");
+    pl->mode = mode;
     if (batch == 0) return 0;
     {   // the kernel addresses one image's input with 32-bit byte offsets (buffer loads)
         const int64_t ih = mode == W2E_CONV_DOWN ? 2 * (int64_t)h + 1 - down_pad : h, iw = mode == W2E_CONV_DOWN ? 2 * (int64_t)w + 1 - down_pad : w;
@@ -1495,28 +1500,23 @@ static int conv_impl(int mode, const float* x, const float* wp, const float* in_
         const int64_t oplane = mode == W2E_CONV_UP ? 4 * ((int64_t)h + 1) * W2E_PLANAR_PITCH(w) : (int64_t)h * w;
         W2E_REQUIRE((int64_t)n_ch * oplane * 4 < ((int64_t)1 << 32) - 16 * oplane, "modconv3x3: one image of the output exceeds 4 GB");
     }
-    hipStream_t s = (hipStream_t)stream;
-
-    ConvParams p{};
-    p.x = x, p.wp = wp, p.in_scale = in_scale, p.out_scale = out_scale, p.y = y;
-    p.noise = noise, p.noise_w = noise_w, p.bias = bias, p.dot_with = dot_with, p.dot_out = dot_out;
+    ConvParams& p = pl->p;
     p.batch = batch, p.K = k_ch, p.N = n_ch, p.H = h, p.W = w;
     if (mode == W2E_CONV_SAME) p.in_h = h, p.in_w = w, p.out_h = h, p.out_w = w;
     else if (mode == W2E_CONV_UP) p.in_h = h, p.in_w = w, p.out_h = 2 * h + 1, p.out_w = 2 * w + 1;
     else p.in_h = 2 * h + 1 - down_pad, p.in_w = 2 * w + 1 - down_pad, p.out_h = h, p.out_w = w, p.in_off = down_pad ? -1 : 0;
-    p.slope = slope;
+#ifdef W2E_TUNING
+    p.tune_skip = opt.tune_skip;
+#endif
 
     // ---- pick the tile configuration with a small cost model.  Unit = MFMA cycles on one SIMD.  A CU works
     // through ceil(wgs/256) workgroups (two resident 256-thread workgroups share its matrix pipes, so they
     // do not go faster than one after the other); a workgroup's time is its per-SIMD MFMA chain plus the
     // part of its staging (barriers, LDS writes) that the register prefetch cannot hide.
     const bool up = mode == W2E_CONV_UP;
-    const Options& opt = options();
     const TileCfg* cfgs = kCfgStd;
-    const int ncfg = kNumCfg;
     const int kc = 8;  // channels per K-chunk = one float4 group per lane-half
     const int kc_max = up ? 16 : kc;  // deepest chunk any workgroup of this launch uses
-    const int wp2 = next_pow2(w);
     int best = -1, best_splits = 1;
     double best_cost = 0.0;
     // no split-K in deterministic mode (no fp32 atomics): the tile is then chosen among the unsplit candidates, not chosen for a
@@ -1525,6 +1525,7 @@ static int conv_impl(int mode, const float* x, const float* wp, const float* in_
     // smallest tile, 64 channels x 64 pixels, leaves CUs without a workgroup -- measured on the IR-SE50 / style-head shapes)
     int sp_max = opt.deterministic ? 1 : 32;
     if (prelu) {
+        const int wp2 = next_pow2(w);
         const int tw6 = wp2 < 32 ? wp2 : 32, th6 = 64 / tw6 > 0 ? 64 / tw6 : 1;
         if ((int64_t)batch * ceil_div(n_ch, 64) * ceil_div(h, th6) * ceil_div(w, tw6) >= 256) sp_max = 1;
     }
@@ -1532,30 +1533,23 @@ static int conv_impl(int mode, const float* x, const float* wp, const float* in_
     // DOWN's slot cap.  The selection loops and a tile forced by tune_cfg both pass through it (a forced tile beyond these limits
     // would stage only part of its patch).
     auto tile_fits = [&](int c, bool all_phase) {
-        const int tn = 32 * cfgs[c].nob * cfgs[c].wo, tm = 32 * (all_phase ? cfgs[c].npb / 4 : cfgs[c].npb) * cfgs[c].wp;
-        const int tw = wp2 < 32 ? wp2 : ((wp2 >= 64 && tm >= 256) ? 64 : 32);
-        const int th = tm / tw;
-        if (th < 1) return false;
-        const int ph = mode == W2E_CONV_SAME ? th + 2 : (up ? th + 1 : 2 * th + 1);
-        const int pw = mode == W2E_CONV_SAME ? tw + 2 : (up ? tw + 1 : 2 * tw + 1);
-        const int nt = 64 * cfgs[c].wo * cfgs[c].wp;
-        const int slots = max_patch_slots(mode, tm, nt);
-        if (all_phase) return sizeof(float) * ((size_t)kc * 9 * tn + (size_t)kc * ph * pw) <= 150 * 1024 && ph * pw <= nt * slots;
+        const TileGeom g = tile_geom(mode, all_phase, cfgs[c], w);
+        if (g.th < 1) return false;
+        const int slots = max_patch_slots(mode, g.tm, g.nt);
+        if (all_phase) return sizeof(float) * ((size_t)kc * 9 * g.tn + (size_t)kc * g.ph * g.pw) <= 150 * 1024 && g.ph * g.pw <= g.nt * slots;
         // deepest K-chunk of this tile (UP: light phases go 16 deep unless the register budget forbids it)
         const int kdeep = (up && cfgs[c].nob * cfgs[c].npb < 8 && slots <= 2) ? 16 : kc;
-        const size_t lds_c = up ? sizeof(float) * ((size_t)32 * tn + (size_t)kdeep * ph * pw)
-                                : sizeof(float) * ((size_t)kc * 9 * tn + (size_t)kc * ph * pw);
+        const size_t lds_c = up ? sizeof(float) * ((size_t)32 * g.tn + (size_t)kdeep * g.ph * g.pw)
+                                : sizeof(float) * ((size_t)kc * 9 * g.tn + (size_t)kc * g.ph * g.pw);
         if (lds_c > 150 * 1024) return false;
         if (mode == W2E_CONV_DOWN && slots > 5) return false;  // prefetch registers: 8 channels x slots
-        return ph * pw <= nt * slots;  // register-prefetch slots per thread
+        return g.ph * g.pw <= g.nt * slots;  // register-prefetch slots per thread
     };
-    for (int c = 0; c < ncfg; ++c) {
-        if (!tile_fits(c, false)) continue;
-        const int tn = 32 * cfgs[c].nob * cfgs[c].wo, tm = 32 * cfgs[c].npb * cfgs[c].wp;
-        const int tw = wp2 < 32 ? wp2 : ((wp2 >= 64 && tm >= 256) ? 64 : 32);
-        const int th = tm / tw;
-        const int nt = 64 * cfgs[c].wo * cfgs[c].wp;
-        const double tiles = (double)batch * ceil_div(n_ch, tn) * ceil_div(h, th) * ceil_div(w, tw);
+    for (int c = 0; c < kNumCfgAll; ++c) {
+        if (!has_tile(up ? kRegUp : kRegStd, c) || !tile_fits(c, false)) continue;
+        const TileGeom g = tile_geom(mode, false, cfgs[c], w);
+        const int tn = g.tn, tm = g.tm, nt = g.nt;
+        const double tiles = (double)batch * ceil_div(n_ch, tn) * ceil_div(h, g.th) * ceil_div(w, g.tw);
         const double waves_per_simd = nt / 256.0;
         const double unit = (double)cfgs[c].nob * cfgs[c].npb * waves_per_simd * (k_ch / 2.0) * 64.0;  // one tap
         const double t_stage0 = (double)ceil_div(k_ch, kc) * 1200.0;
@@ -1587,18 +1581,14 @@ static int conv_impl(int mode, const float* x, const float* wp, const float* in_
     // UP: the all-phase form (one staged patch, 9 taps, 4 phases x NPB/4 pixel blocks per wave) as the alternative
     bool use_all = false;
     if (up) {
-        static const int kAll[] = {0, 1, 2, 4, 8, 11};
         const int tune_all = opt.tune_upall;  // -1 the library's choice, 0 never, 1 always
         int best_a = -1, best_a_splits = 1;
         double best_a_cost = 0.0;
-        for (int ci = 0; ci < 6 && tune_all != 0; ++ci) {
-            const int c = kAll[ci];
-            if (!tile_fits(c, true)) continue;
-            const int tn = 32 * cfgs[c].nob * cfgs[c].wo, tm = 32 * (cfgs[c].npb / 4) * cfgs[c].wp;
-            const int tw = wp2 < 32 ? wp2 : ((wp2 >= 64 && tm >= 256) ? 64 : 32);
-            const int th = tm / tw;
-            const int nt = 64 * cfgs[c].wo * cfgs[c].wp;
-            const double tiles = (double)batch * ceil_div(n_ch, tn) * ceil_div(h, th) * ceil_div(w, tw);
+        for (int c = 0; c < kNumCfgAll && tune_all != 0; ++c) {
+            if (!has_tile(kRegUpAll, c) || !tile_fits(c, true)) continue;
+            const TileGeom g = tile_geom(mode, true, cfgs[c], w);
+            const int tn = g.tn, tm = g.tm, nt = g.nt;
+            const double tiles = (double)batch * ceil_div(n_ch, tn) * ceil_div(h, g.th) * ceil_div(w, g.tw);
             const double unit = (double)cfgs[c].nob * (cfgs[c].npb / 4) * (nt / 256.0) * (k_ch / 2.0) * 64.0;  // one tap
             const double t_stage = (double)ceil_div(k_ch, kc) * 1200.0;
             for (int sp = 1; sp <= sp_max; sp *= 2) {
@@ -1622,36 +1612,29 @@ static int conv_impl(int mode, const float* x, const float* wp, const float* in_
     const int tune_x3 = prelu ? 0 : opt.conv_precision;  // (the bias/PReLU epilogue is instantiated for the fp32 register pipeline)
     // DOWN in that mode: the 128x256 tile (9) is the one whose stride-2 patch fits beside the bf16 operand images in LDS (156 KB)
     if (tune_x3 == 1 && mode == W2E_CONV_DOWN && (int64_t)h * w >= 4096 && n_ch >= 128 && best >= 0) best = 9, best_splits = 1;  // (N = 64 fills half the tile: slower than fp32)
-#ifdef W2E_TUNING
-    p.tune_skip = opt.tune_skip;
-#endif
     if (opt.tune_cfg >= 0) {  // tests / tools/layer_bench.py: "<cfg>[,<splits>[,<mode>]]", third field: only launches of that mode
         const int fc = opt.tune_cfg, fs = opt.tune_cfg_splits, fm = opt.tune_cfg_mode;
-        if (fc < (use_all ? kNumCfgAll : ncfg) && (fm < 0 || fm == mode)) {
+        if (fc < (use_all ? kNumCfgAll : kNumCfg) && (fm < 0 || fm == mode)) {
             W2E_REQUIRE(tile_fits(fc, use_all), "modconv3x3: tile %d (forced by tune_cfg) does not fit mode %d%s, K %d N %d %dx%d (LDS budget / patch slots)",
                         fc, mode, use_all ? " (all-phase)" : "", k_ch, n_ch, h, w);
             best = fc, best_splits = fs > 0 ? fs : 1;
         }
     }
     if (opt.deterministic) best_splits = 1;  // no fp32 atomics onto y: one workgroup owns every output element
-    const bool print = opt.tune_print && !(plan && plan->quiet);
-    if (print) fprintf(stderr, "modconv mode %d%s K %d N %d %dx%d B %d -> cfg %d splits %d\n", mode, use_all ? " (all-phase)" : "", k_ch, n_ch, h, w, batch, best, best_splits);
     W2E_REQUIRE(best >= 0, "modconv3x3: no tile configuration for N=%d H=%d W=%d", n_ch, h, w);
     const TileCfg cfg = cfgs[best];
     W2E_REQUIRE(!use_all || cfg.npb >= 4, "modconv3x3: tile %d has no all-phase form (forced by tune_cfg)", best);  // (a forced tile: 0 pixel blocks per phase)
-    const int tn = 32 * cfg.nob * cfg.wo, tm = 32 * (use_all ? cfg.npb / 4 : cfg.npb) * cfg.wp;
-    p.tw = wp2 < 32 ? wp2 : ((wp2 >= 64 && tm >= 256) ? 64 : 32);
-    p.th = tm / p.tw;
+    const TileGeom g = tile_geom(mode, use_all, cfg, w);
+    p.tw = g.tw, p.th = g.th;
     p.tw_log2 = 0;
     while ((1 << p.tw_log2) < p.tw) ++p.tw_log2;
-    p.tiles_x = (int)ceil_div(w, p.tw), p.tiles_y = (int)ceil_div(h, p.th), p.tiles_n = (int)ceil_div(n_ch, tn);
-    if (mode == W2E_CONV_SAME) p.ph = p.th + 2, p.pw = p.tw + 2;
-    else if (up) p.ph = p.th + 1, p.pw = p.tw + 1;
-    else p.ph = 2 * p.th + 1, p.pw = 2 * p.tw + 1;
+    p.tiles_x = (int)ceil_div(w, p.tw), p.tiles_y = (int)ceil_div(h, p.th), p.tiles_n = (int)ceil_div(n_ch, g.tn);
+    p.ph = g.ph, p.pw = g.pw;
     p.plane = p.ph * p.pw;
     p.pw_magic = (unsigned)(((uint64_t)1 << 32) / (unsigned)p.pw + 1);
     W2E_REQUIRE(p.plane < 65536, "modconv3x3: patch too large");
-    const int nt_best = 64 * cfg.wo * cfg.wp;
+    const int plane16 = (p.plane + 15) & ~15;  // the DMA pipeline's plane
+    const int launch_mode = use_all ? CONV_UPALL : mode;
     // LDS-DMA pipeline (two LDS stages + the in_scale table): where it is instantiated and fits
     // W2E_TUNE_DMA: 0 never, 1 wherever instantiated; default = where it measured faster (tools/layer_bench.py, batch 4):
     // the 512-thread 8-accumulator SAME tiles (+1.5-3 %) and the all-phase UP tiles 0 / 1 / 11 (+2-5 %; since the DMA is issued piecewise
@@ -1661,133 +1644,89 @@ static int conv_impl(int mode, const float* x, const float* wp, const float* in_
     bool use_dma = false;
     size_t lds_dma = 0;
     const bool dma_auto = prelu ? false : use_all ? (best == 0 || best == 1 || best == 11) : (mode == W2E_CONV_SAME && best <= 2);
-    if (!prelu && (tune_dma == 1 || (tune_dma < 0 && dma_auto)) && !(up && !use_all) && dma_has_cfg(use_all, best)) {
-        const int plane16 = (p.plane + 15) & ~15;  // whole DMA wave-instructions (16 pixels x 4 channels) per plane
-        lds_dma = sizeof(float) * (2 * ((size_t)kc * 9 * tn + (size_t)kc * plane16) + (size_t)((k_ch + 7) / 8) * 8);
-        const int slots = (int)ceil_div(4 * plane16, nt_best);
-        // (the pipeline addresses channels up to K+7 of an image with 32-bit byte offsets: they must not wrap)
-        const bool off_ok = ((int64_t)k_ch + 8) * p.in_h * p.in_w * 4 < ((int64_t)1 << 32);
-        if (off_ok && lds_dma <= 150 * 1024 && slots <= 4 * max_patch_slots(up ? W2E_CONV_UP : mode, tm, nt_best) + 1) use_dma = true, p.plane = plane16;
-        if (print) fprintf(stderr, "  lds-dma pipeline: %s (%zu B LDS, %d slots)\n", use_dma ? "yes" : "no", lds_dma, slots);
+    if (!prelu && (tune_dma == 1 || (tune_dma < 0 && dma_auto)) && has_tile(tile_mask(launch_mode, EPI_PLAIN, 1), best)) {
+        lds_dma = sizeof(float) * (2 * ((size_t)kc * 9 * g.tn + (size_t)kc * plane16) + (size_t)((k_ch + 7) / 8) * 8);
+        use_dma = dma_fits(mode, p, g, &pl->dma_slots) && lds_dma <= 150 * 1024;
+        if (use_dma) p.plane = plane16;
+        pl->dma_tried = true, pl->dma_taken = use_dma, pl->dma_lds = lds_dma;
     }
-    const int kdeep_best = (up && !use_all && cfg.nob * cfg.npb < 8 && max_patch_slots(mode, tm, nt_best) <= 2) ? 16 : kc;
-    size_t lds = (up && !use_all) ? sizeof(float) * ((size_t)32 * tn + (size_t)kdeep_best * p.plane)
-                                  : sizeof(float) * ((size_t)kc * 9 * tn + (size_t)kc * p.plane);
+    const int kdeep_best = (up && !use_all && cfg.nob * cfg.npb < 8 && max_patch_slots(mode, g.tm, g.nt) <= 2) ? 16 : kc;
+    size_t lds = (up && !use_all) ? sizeof(float) * ((size_t)32 * g.tn + (size_t)kdeep_best * p.plane)
+                                  : sizeof(float) * ((size_t)kc * 9 * g.tn + (size_t)kc * p.plane);
+    // bf16x3 runs in the DMA pipeline: its tiles that are not DMA tiles by default (DOWN's, the all-phase UP ones, SAME's 32x512 tile)
+    // take the pipeline for this mode
+    const bool x3_tile = tune_x3 == 1 && has_tile(tile_mask(launch_mode, EPI_PLAIN, 2), best);
+    if (x3_tile && !use_dma && (mode != W2E_CONV_SAME || best == 8)) {
+        int slots;
+        use_dma = dma_fits(mode, p, g, &slots);
+        if (use_dma) p.plane = plane16;  // (kept when DOWN falls back to the register pipeline below: a wider plane stride, nothing else)
+    }
     bool use_x3 = false;
-    if (tune_x3 == 1 && !use_dma && mode == W2E_CONV_DOWN && best == 9) {  // DOWN: not a DMA tile by default
-        const int plane16 = (p.plane + 15) & ~15;
-        const int slots = (int)ceil_div(4 * plane16, nt_best);
-        const bool off_ok = ((int64_t)k_ch + 8) * p.in_h * p.in_w * 4 < ((int64_t)1 << 32);
-        if (off_ok && slots <= 4 * max_patch_slots(mode, tm, nt_best) + 1) use_dma = true, p.plane = plane16;
-    }
-    if (tune_x3 == 1 && !use_dma && mode == W2E_CONV_SAME && best == 8 && dma_has_cfg(false, best)) {  // the 32x512 tile: not a DMA tile by default
-        const int plane16 = (p.plane + 15) & ~15;
-        const int slots = (int)ceil_div(4 * plane16, nt_best);
-        const bool off_ok = ((int64_t)k_ch + 8) * p.in_h * p.in_w * 4 < ((int64_t)1 << 32);
-        if (off_ok && slots <= 4 * max_patch_slots(mode, tm, nt_best) + 1) use_dma = true, p.plane = plane16;
-    }
-    if (tune_x3 == 1 && !use_dma && use_all && (best <= 2 || best == 11)) {  // all-phase UP tiles that are not DMA tiles by default
-        const int plane16 = (p.plane + 15) & ~15;
-        const int slots = (int)ceil_div(4 * plane16, nt_best);
-        const bool off_ok = ((int64_t)k_ch + 8) * p.in_h * p.in_w * 4 < ((int64_t)1 << 32);
-        if (off_ok && slots <= 4 * max_patch_slots(W2E_CONV_UP, tm, nt_best) + 1) use_dma = true, p.plane = plane16;
-    }
-    if (tune_x3 == 1 && use_dma && ((mode == W2E_CONV_SAME && (best <= 2 || best == 8)) || (use_all && (best <= 2 || best == 11)) ||
-                                    (mode == W2E_CONV_DOWN && best == 9))) {
+    if (x3_tile && use_dma) {
         // fp32 staging area + bf16 operand images (20*tn + 2*plane 16-byte entries) + the in_scale table
-        lds_dma = sizeof(float) * (((size_t)kc * 9 * tn + (size_t)kc * p.plane) + 4 * ((size_t)20 * tn + 2 * (size_t)p.plane) + (size_t)((k_ch + 7) / 8) * 8);
+        lds_dma = sizeof(float) * (((size_t)kc * 9 * g.tn + (size_t)kc * plane16) + 4 * ((size_t)20 * g.tn + 2 * (size_t)plane16) + (size_t)((k_ch + 7) / 8) * 8);
         use_x3 = lds_dma <= 160 * 1024;
         if (!use_x3 && mode == W2E_CONV_DOWN) use_dma = false;  // (DOWN takes the DMA pipeline only for this mode)
-        if (print) fprintf(stderr, "  bf16x3: %s (%zu B LDS)\n", use_x3 ? "yes" : "no", lds_dma);
+        pl->x3_lds = lds_dma;
     }
     if (use_dma) lds = lds_dma;
     W2E_REQUIRE(lds <= 160 * 1024, "modconv3x3: tile needs %zu B of LDS", lds);
     const int k_gran = use_all ? kc : kc_max;
     p.k_per = (int)(ceil_div(ceil_div(k_ch, best_splits), k_gran) * k_gran);
     p.splits = (int)ceil_div(k_ch, p.k_per);
-    if (print && !plan) {  // the variant that runs (tests/test_gpu_conv_variants.py keys its coverage census on this line); a split
-                           // activation / bias + PReLU runs as the plain kernel followed by an elementwise pass ("act_pass" / "prelu_pass")
-        const char* epi = prelu ? (p.splits > 1 ? "prelu_pass" : "prelu") : act ? (p.splits > 1 ? "act_pass" : "act") : dot_with ? "dot" : "plain";
-        fprintf(stderr, "modconv variant mode %d all %d cfg %d splits %d dma %d x3 %d epi %s\n", mode, use_all ? 1 : 0, best, p.splits,
-                use_dma ? 1 : 0, use_x3 ? 1 : 0, epi);
-    }
     if (up) {
         // border units (one wave each): image x 32-channel block x 32-position block of the last row (W+1 positions) / column (H)
         p.groups_row = (int)ceil_div(w + 1, 32), p.groups_col = (int)ceil_div(h, 32);
         const int64_t border = (int64_t)batch * (p.groups_row + p.groups_col) * ceil_div(n_ch, 32);  // one workgroup per unit
         W2E_REQUIRE(border < ((int64_t)1 << 31), "modconv3x3: %lld border units are too many", (long long)border);
         p.border_wgs = (int)border;
-        if (lds < (size_t)(nt_best / 64) * 32 * 64 * sizeof(float)) lds = (size_t)(nt_best / 64) * 32 * 64 * sizeof(float);  // their join buffer
+        if (lds < (size_t)(g.nt / 64) * 32 * 64 * sizeof(float)) lds = (size_t)(g.nt / 64) * 32 * 64 * sizeof(float);  // their join buffer
     }
     const int64_t grid = (int64_t)p.tiles_x * p.tiles_y * p.tiles_n * batch * ((up && !use_all) ? 4 : 1) * p.splits + p.border_wgs;
-    W2E_REQUIRE(grid < ((int64_t)1 << 31), "modconv3x3: grid of %lld workgroups is too large", (long long)grid);  // (cast to int at every launch below)
-    if (plan) {  // the caller launches (or only asked)
-        plan->p = p, plan->cfg = best, plan->use_dma = use_dma, plan->use_x3 = use_x3, plan->lds = lds, plan->grid = grid;
-        return 0;
-    }
+    W2E_REQUIRE(grid < ((int64_t)1 << 31), "modconv3x3: grid of %lld workgroups is too large", (long long)grid);  // (cast to int at every launch)
+    pl->use_all = use_all, pl->cfg = best, pl->req_splits = best_splits, pl->use_dma = use_dma, pl->use_x3 = use_x3, pl->lds = lds, pl->grid = grid;
+    return 0;
+}
+
+// The tune_print lines of a planned launch: the layer line, what the pipeline choice looked at, and (epi != EPI_DOT_RGB: that entry
+// point prints a line of its own format) the variant that runs -- tests/test_gpu_conv_variants.py keys its coverage census on it; a
+// split activation / bias + PReLU runs as the plain kernel followed by an elementwise pass ("act_pass" / "prelu_pass").
+static void conv_print(const ConvPlan& pl, int epi) {
+    const ConvParams& p = pl.p;
+    fprintf(stderr, "modconv mode %d%s K %d N %d %dx%d B %d -> cfg %d splits %d\n", pl.mode, pl.use_all ? " (all-phase)" : "", p.K, p.N, p.H, p.W, p.batch,
+            pl.cfg, pl.req_splits);
+    if (pl.dma_tried) fprintf(stderr, "  lds-dma pipeline: %s (%zu B LDS, %d slots)\n", pl.dma_taken ? "yes" : "no", pl.dma_lds, pl.dma_slots);
+    if (pl.x3_lds) fprintf(stderr, "  bf16x3: %s (%zu B LDS)\n", pl.use_x3 ? "yes" : "no", pl.x3_lds);
+    if (epi == EPI_DOT_RGB) return;
+    const char* name = epi == EPI_PRELU ? (p.splits > 1 ? "prelu_pass" : "prelu") : epi == EPI_ACT ? (p.splits > 1 ? "act_pass" : "act") : epi == EPI_DOT ? "dot" : "plain";
+    fprintf(stderr, "modconv variant mode %d all %d cfg %d splits %d dma %d x3 %d epi %s\n", pl.mode, pl.use_all ? 1 : 0, pl.cfg, p.splits,
+            pl.use_dma ? 1 : 0, pl.use_x3 ? 1 : 0, name);
+}
+
 #ifdef W2E_TUNING
-    // tuning aid: W2E_TUNE_CLOCK=1 stamps every workgroup and reports the in-kernel shader clock (s_memtime ticks per
-    // 100 MHz s_memrealtime tick) of every 64th launch -- the DVFS-limited clock is what an MFMA-bound kernel is priced by
-    const bool tune_clock = opt.tune_clock != 0;
-    static unsigned long long* stamp_buf = nullptr;
-    static int64_t stamp_cap = 0, stamp_calls = 0;
-    bool stamped = false;
-    if (tune_clock && (stamp_calls++ & 63) == 63) {
-        if (grid > stamp_cap) {
-            if (stamp_buf) (void)hipFree(stamp_buf);
-            stamp_cap = grid, stamp_buf = nullptr;
-            if (hipMalloc((void**)&stamp_buf, sizeof(unsigned long long) * STAMP_STRIDE * (size_t)stamp_cap) != hipSuccess) stamp_buf = nullptr, stamp_cap = 0;
+// tuning aid: W2E_TUNE_CLOCK=1 stamps every workgroup and reports the in-kernel shader clock (s_memtime ticks per
+// 100 MHz s_memrealtime tick) of every 64th launch -- the DVFS-limited clock is what an MFMA-bound kernel is priced by
+struct ClockStamps {
+    bool on = false;
+    // before the launch: every 64th call gets a zeroed stamp buffer in p->stamps
+    void begin(const ConvPlan& pl, ConvParams* p, hipStream_t s) {
+        static int64_t cap = 0, calls = 0;
+        if (!options().tune_clock || (calls++ & 63) != 63) return;
+        if (pl.grid > cap) {
+            if (buf) (void)hipFree(buf);
+            cap = pl.grid, buf = nullptr;
+            if (hipMalloc((void**)&buf, sizeof(unsigned long long) * STAMP_STRIDE * (size_t)cap) != hipSuccess) buf = nullptr, cap = 0;
         }
-        if (stamp_buf && zero_async(stamp_buf, sizeof(unsigned long long) * STAMP_STRIDE * (size_t)grid, s) == hipSuccess) p.stamps = stamp_buf, stamped = true;
+        if (buf && zero_async(buf, sizeof(unsigned long long) * STAMP_STRIDE * (size_t)pl.grid, s) == hipSuccess) p->stamps = buf, on = true;
     }
-#endif
-    if (p.splits > 1 &&
-        zero_async(y, sizeof(float) * (size_t)batch * n_ch * (up ? 4 * (h + 1) * W2E_PLANAR_PITCH(w) : p.out_h * p.out_w), s) != hipSuccess) {
-        set_error("modconv3x3: memset failed");
-        return 2;
-    }
-    bool ok = false;
-    if (use_x3 && use_all) {
-        ok = launch_x3_up(best, p, (int)grid, lds, s);
-    } else if (use_x3 && mode == W2E_CONV_DOWN) {
-        if (dot_with) ok = launch_x3_down<EPI_DOT>(best, p, (int)grid, lds, s);
-        else ok = launch_x3_down<EPI_PLAIN>(best, p, (int)grid, lds, s);
-    } else if (use_x3) {
-        if (act && p.splits == 1) ok = launch_x3<EPI_ACT>(best, p, (int)grid, lds, s);
-        else if (dot_with) ok = launch_x3<EPI_DOT>(best, p, (int)grid, lds, s);
-        else ok = launch_x3<EPI_PLAIN>(best, p, (int)grid, lds, s);
-    } else if (use_dma) {
-        if (mode == W2E_CONV_SAME) {
-            if (act && p.splits == 1) ok = launch_mode_dma<W2E_CONV_SAME, EPI_ACT, 8>(best, p, (int)grid, lds, s);
-            else if (dot_with) ok = launch_mode_dma<W2E_CONV_SAME, EPI_DOT, 8>(best, p, (int)grid, lds, s);
-            else ok = launch_mode_dma<W2E_CONV_SAME, EPI_PLAIN, 8>(best, p, (int)grid, lds, s);
-        } else if (up) {
-            ok = launch_mode_dma<CONV_UPALL, EPI_PLAIN, 8>(best, p, (int)grid, lds, s);
-        } else {
-            if (dot_with) ok = launch_mode_dma<W2E_CONV_DOWN, EPI_DOT, 8>(best, p, (int)grid, lds, s);
-            else ok = launch_mode_dma<W2E_CONV_DOWN, EPI_PLAIN, 8>(best, p, (int)grid, lds, s);
-        }
-    } else if (prelu && p.splits == 1) {
-        if (mode == W2E_CONV_SAME) ok = launch_mode<W2E_CONV_SAME, EPI_PRELU, 8>(best, p, (int)grid, lds, s);
-        else ok = launch_mode<W2E_CONV_DOWN, EPI_PRELU, 8>(best, p, (int)grid, lds, s);
-    } else if (mode == W2E_CONV_SAME) {
-        if (act && p.splits == 1) ok = launch_mode<W2E_CONV_SAME, EPI_ACT, 8>(best, p, (int)grid, lds, s);
-        else if (dot_with) ok = launch_mode<W2E_CONV_SAME, EPI_DOT, 8>(best, p, (int)grid, lds, s);
-        else ok = launch_mode<W2E_CONV_SAME, EPI_PLAIN, 8>(best, p, (int)grid, lds, s);
-    } else if (up) {
-        if (use_all) ok = launch_mode<CONV_UPALL, EPI_PLAIN, 8>(best, p, (int)grid, lds, s);
-        else ok = launch_mode<W2E_CONV_UP, EPI_PLAIN, 8>(best, p, (int)grid, lds, s);
-    } else {
-        if (dot_with) ok = launch_mode<W2E_CONV_DOWN, EPI_DOT, 8>(best, p, (int)grid, lds, s);
-        else ok = launch_mode<W2E_CONV_DOWN, EPI_PLAIN, 8>(best, p, (int)grid, lds, s);
-    }
-    W2E_REQUIRE(ok, "modconv3x3: internal: configuration %d not instantiated", best);
-    W2E_LAUNCH_CHECK("modconv3x3");
-#ifdef W2E_TUNING
-    if (stamped) {
+    // after it: synchronise, read the stamps back, report
+    void report(const ConvPlan& pl, hipStream_t s) const {
+        if (!on) return;
+        const ConvParams& p = pl.p;
+        const int64_t grid = pl.grid;
         unsigned long long* hb = (unsigned long long*)malloc(sizeof(unsigned long long) * STAMP_STRIDE * (size_t)grid);
         if (hb && hipStreamSynchronize(s) == hipSuccess &&
-            hipMemcpy(hb, stamp_buf, sizeof(unsigned long long) * STAMP_STRIDE * (size_t)grid, hipMemcpyDeviceToHost) == hipSuccess) {
+            hipMemcpy(hb, buf, sizeof(unsigned long long) * STAMP_STRIDE * (size_t)grid, hipMemcpyDeviceToHost) == hipSuccess) {
             double ticks = 0.0, real = 0.0;
             unsigned long long first = ~0ull, last = 0;
             int64_t n = 0;
@@ -1800,24 +1739,62 @@ static int conv_impl(int mode, const float* x, const float* wp, const float* in_
                 if (e[3] > last) last = e[3];
                 for (int q = 4; q < STAMP_STRIDE; ++q) ph[q - 4] += (double)e[q];
             }
-            if (n && STAMP_STRIDE == 8 && use_dma)
+            if (n && STAMP_STRIDE == 8 && pl.use_dma)
                 fprintf(stderr, "modconv phases (wave 0, mean cycles per workgroup): K loop %.0f, of it vmcnt(0) wait %.0f, barrier %.0f, DMA issue %.0f\n",
                         ph[2] / n, ph[0] / n, ph[1] / n, ph[3] / n);
             if (n) fprintf(stderr, "modconv clock: mode %d K %d N %d %dx%d cfg %d%s: %.3f GHz in-kernel (%lld workgroups, mean %.0f cycles each, launch span %.1f us)\n",
-                           mode, k_ch, n_ch, h, w, best, use_dma ? " dma" : "", ticks / real * 0.1, (long long)n, ticks / n, (double)(last - first) * 0.01);
+                           pl.mode, p.K, p.N, p.H, p.W, pl.cfg, pl.use_dma ? " dma" : "", ticks / real * 0.1, (long long)n, ticks / n, (double)(last - first) * 0.01);
         }
         free(hb);
     }
+    static inline unsigned long long* buf = nullptr;
+};
 #endif
-    if (act && p.splits > 1) {  // the activation needs the complete sum: one in-place elementwise pass
-        const int rc = w2e_bias_act_fwd(y, bias, noise, noise_w, y, batch, n_ch, (int64_t)h * w, 0.2f, 1.4142135623730951f, stream);
-        if (rc != 0) return rc;
+
+// The side effects of a planned launch: the split-K memset, the kernel, and the elementwise pass a split activation / bias + PReLU needs.
+// epi: the epilogue the caller asked for (EPI_PLAIN / EPI_ACT / EPI_DOT / EPI_PRELU).
+static int conv_launch(const ConvPlan& pl, const float* x, const float* wp, const float* in_scale, const float* out_scale, float* y,
+                       const float* noise, const float* noise_w, const float* bias, const float* dot_with, float* dot_out, const float* slope,
+                       int epi, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    ConvParams p = pl.p;
+    p.x = x, p.wp = wp, p.in_scale = in_scale, p.out_scale = out_scale, p.y = y;
+    p.noise = noise, p.noise_w = noise_w, p.bias = bias, p.dot_with = dot_with, p.dot_out = dot_out, p.slope = slope;
+#ifdef W2E_TUNING
+    ClockStamps stamps;
+    stamps.begin(pl, &p, s);
+#endif
+    if (p.splits > 1 &&
+        zero_async(y, sizeof(float) * (size_t)p.batch * p.N * (pl.mode == W2E_CONV_UP ? 4 * (p.H + 1) * W2E_PLANAR_PITCH(p.W) : p.out_h * p.out_w), s) != hipSuccess) {
+        set_error("modconv3x3: memset failed");
+        return 2;
     }
-    if (prelu && p.splits > 1) {  // likewise bias + PReLU (the low-resolution layers of IR-SE50 and of the encoders' style heads: a
-                                  // handful of tiles with a K*9/2-long MFMA chain each unless K is split)
-        const int rc = w2e_affine_act_fwd(y, nullptr, bias, slope, y, batch, n_ch, (int64_t)p.out_h * p.out_w, stream);
-        if (rc != 0) return rc;
-    }
+    const bool pass = p.splits > 1 && (epi == EPI_ACT || epi == EPI_PRELU);  // these need the complete sum: the plain kernel, then one in-place elementwise pass
+    const int rc = launch_plan(pl, p, pass ? EPI_PLAIN : epi, s);
+    if (rc != 0) return rc;
+    W2E_LAUNCH_CHECK("modconv3x3");
+#ifdef W2E_TUNING
+    stamps.report(pl, s);
+#endif
+    if (pass && epi == EPI_ACT) return w2e_bias_act_fwd(y, bias, noise, noise_w, y, p.batch, p.N, (int64_t)p.H * p.W, 0.2f, 1.4142135623730951f, stream);
+    // bias + PReLU: the low-resolution layers of IR-SE50 and of the encoders' style heads (a handful of tiles with a K*9/2-long MFMA
+    // chain each unless K is split)
+    if (pass) return w2e_affine_act_fwd(y, nullptr, bias, slope, y, p.batch, p.N, (int64_t)p.out_h * p.out_w, stream);
+    return 0;
+}
+
+}  // namespace w2e
+
+using namespace w2e;
+
+extern "C" int w2e_conv_pack(const float* weight, float* wp, int cout, int cin, float scale, int transpose, int flip,
+                             void* stream) {
+    W2E_REQUIRE(weight && wp, "conv_pack: null tensor");
+    W2E_REQUIRE(cout > 0 && cin > 0, "conv_pack: bad dims");
+    const int64_t total = (int64_t)(((transpose ? cout : cin) + 7) / 8) * 72 * (transpose ? cin : cout) * 4;
+    conv_pack_kernel<<<stream_grid(total, 256), 256, 0, (hipStream_t)stream>>>(weight, wp, cout, cin, scale, transpose,
+                                                                             flip);
+    W2E_LAUNCH_CHECK("conv_pack");
     return 0;
 }
 
@@ -1828,13 +1805,24 @@ static int conv_impl(int mode, const float* x, const float* wp, const float* in_
                 name ": UP output with a row pitch of %d floats, this library's layout has %d (W2E_PLANAR_PITCH, ABI %d): rebuild the caller", \
                 y_pitch, W2E_PLANAR_PITCH(w), W2E_VERSION)
 
+// Both entry points: validate -> plan -> print -> launch.
 extern "C" int w2e_modconv3x3(int mode, const float* x, const float* wp, const float* in_scale, const float* out_scale,
                               float* y, int batch, int k_ch, int n_ch, int h, int w, int y_pitch, int act, const float* noise,
                               const float* noise_w, const float* bias, const float* dot_with, float* dot_out,
                               void* stream) {
     W2E_CHECK_UP_PITCH("modconv3x3");
-    return conv_impl(mode, x, wp, in_scale, out_scale, y, batch, k_ch, n_ch, h, w, act, noise, noise_w, bias, dot_with, dot_out,
-                     nullptr, 0, 0, stream);
+    W2E_REQUIRE(x && wp && y, "modconv3x3: null tensor");
+    W2E_REQUIRE(!(act && mode != W2E_CONV_SAME), "modconv3x3: fused activation only in SAME mode");
+    W2E_REQUIRE(!(dot_with && (act || mode == W2E_CONV_UP)), "modconv3x3: dot epilogue only without act, not in UP mode");
+    W2E_REQUIRE((dot_with == nullptr) == (dot_out == nullptr), "modconv3x3: dot_with and dot_out go together");
+    W2E_REQUIRE(!noise || noise_w, "modconv3x3: noise without noise_w");
+    const Options& opt = options();
+    ConvPlan pl;
+    const int rc = conv_plan(mode, batch, k_ch, n_ch, h, w, 0, 0, opt, &pl);
+    if (rc != 0 || batch == 0) return rc;
+    const int epi = act ? EPI_ACT : dot_with ? EPI_DOT : EPI_PLAIN;
+    if (opt.tune_print) conv_print(pl, epi);
+    return conv_launch(pl, x, wp, in_scale, out_scale, y, noise, noise_w, bias, dot_with, dot_out, nullptr, epi, stream);
 }
 
 extern "C" int w2e_conv3x3(int mode, const float* x, const float* wp, const float* in_scale, const float* out_scale, float* y,
@@ -1843,15 +1831,33 @@ extern "C" int w2e_conv3x3(int mode, const float* x, const float* wp, const floa
     W2E_CHECK_UP_PITCH("conv3x3");
     const int prelu = (bias || slope) ? 1 : 0;
     W2E_REQUIRE(!(prelu && mode == W2E_CONV_UP), "conv3x3: no bias / PReLU epilogue in UP mode");
-    return conv_impl(mode, x, wp, in_scale, out_scale, y, batch, k_ch, n_ch, h, w, 0, nullptr, nullptr, bias, nullptr, nullptr,
-                     slope, prelu, down_pad, stream);
+    W2E_REQUIRE(x && wp && y, "modconv3x3: null tensor");
+    const Options& opt = options();
+    ConvPlan pl;
+    const int rc = conv_plan(mode, batch, k_ch, n_ch, h, w, prelu, down_pad, opt, &pl);
+    if (rc != 0 || batch == 0) return rc;
+    const int epi = prelu ? EPI_PRELU : EPI_PLAIN;
+    if (opt.tune_print) conv_print(pl, epi);
+    return conv_launch(pl, x, wp, in_scale, out_scale, y, nullptr, nullptr, bias, nullptr, nullptr, slope, epi, stream);
+}
+
+extern "C" int w2e_conv3x3_plan(int mode, int batch, int k_ch, int n_ch, int h, int w, int prelu, int down_pad, int64_t* out) {
+    W2E_REQUIRE(out != nullptr, "conv3x3_plan: null argument");
+    ConvPlan pl;
+    const int rc = conv_plan(mode, batch, k_ch, n_ch, h, w, prelu, down_pad, options(), &pl);
+    if (rc != 0) return rc;
+    const ConvParams& p = pl.p;
+    const int64_t fields[W2E_CONV_PLAN_FIELDS] = {pl.use_all, pl.cfg, p.splits, p.k_per, pl.use_dma, pl.use_x3, (int64_t)pl.lds, pl.grid,
+                                                  p.th, p.tw, p.tiles_x, p.tiles_y, p.tiles_n, p.plane, p.border_wgs};
+    for (int i = 0; i < W2E_CONV_PLAN_FIELDS; ++i) out[i] = fields[i];
+    return 0;
 }
 
 // ---- the all-phase UP conv with the 4x4 blur and the StyledConv epilogue in the tile's epilogue (modconv_kernel UPB): one launch
 // writes the final [B,N,2H,2W] tensor, the intermediate T never exists.  Tile {1,8,1,8} as 16 x 32 input positions, of which a tile owns
 // 14 x 30 (the rest is the recomputed halo of the blur): 1.30x the K-loop work of the two-launch form at 512^2, 1.5x at 64^2.
 namespace w2e {
-constexpr int UPB_TH = 16, UPB_TW = 32;
+constexpr int UPB_TH = 16, UPB_TW = 32, UPB_CFG = 11;
 
 // Why the fused form cannot take a launch, or nullptr.  (fp32 only; no split-K: the blur needs the complete sum.)
 static const char* upblur_refusal(const Options& opt, int batch, int k_ch, int n_ch, int h, int w) {
@@ -1881,6 +1887,7 @@ extern "C" int w2e_modconv_upblur_plan(int batch, int k_ch, int n_ch, int h, int
     return 0;
 }
 
+// (Its fixed tile and geometry are not a product of the cost model: the parameters are built by hand, not by conv_plan.)
 extern "C" int w2e_modconv_upblur(const float* x, const float* wp, const float* in_scale, const float* out_scale, const float* kern,
                                   float* y, int batch, int k_ch, int n_ch, int h, int w, const float* noise, const float* noise_w,
                                   const float* bias, void* stream) {
@@ -1912,54 +1919,28 @@ extern "C" int w2e_modconv_upblur(const float* x, const float* wp, const float* 
     const int64_t grid = (int64_t)p.tiles_x * p.tiles_y * p.tiles_n * batch;
     if (opt.tune_print) {  // the layer line every conv launch prints (it is still one of the step's 3x3 conv launches), then a variant line
                            // of its own format: the census of tests/test_gpu_upblur.py keys on it
-        fprintf(stderr, "modconv mode %d (all-phase) K %d N %d %dx%d B %d -> cfg 11 splits 1\n", W2E_CONV_UP, k_ch, n_ch, h, w, batch);
-        fprintf(stderr, "modconv upblur variant cfg 11 th %d tw %d groups %d vec %d K %d N %d %dx%d B %d\n", p.th, p.tw, groups, p.vec4, k_ch, n_ch, h, w, batch);
+        fprintf(stderr, "modconv mode %d (all-phase) K %d N %d %dx%d B %d -> cfg %d splits 1\n", W2E_CONV_UP, k_ch, n_ch, h, w, batch, UPB_CFG);
+        fprintf(stderr, "modconv upblur variant cfg %d th %d tw %d groups %d vec %d K %d N %d %dx%d B %d\n", UPB_CFG, p.th, p.tw, groups, p.vec4, k_ch, n_ch, h, w, batch);
     }
-    launch_cfg<CONV_UPALL, EPI_PLAIN, 1, 8, 1, 8, 8, 1, 1>(p, (int)grid, lds, (hipStream_t)stream);
+    constexpr TileCfg t = kCfgStd[UPB_CFG];
+    const int rc = launch_cfg<CONV_UPALL, EPI_PLAIN, t.nob, t.npb, t.wo, t.wp, 8, 1, 1>(p, (int)grid, lds, (hipStream_t)stream);
+    if (rc != 0) return rc;
     W2E_LAUNCH_CHECK("modconv_upblur");
     return 0;
 }
 
 // ---- the stride-2 dgrad conv of an up-sampling StyledConv with the ToRGB backward of the level it writes in its dot epilogue
 // (modconv_kernel<W2E_CONV_DOWN, EPI_DOT_RGB, ...>): the launch stores gpre instead of the input gradient, and the second pass
-// over x and that gradient (torgb_bwd_kernel<., true, true>) does not run.  The tile is the one conv_impl's cost model picks for the
-// shape (or tune_cfg forces); the epilogue exists for every DOWN tile that model can pick, in both pipelines where both exist.
+// over x and that gradient (torgb_bwd_kernel<., true, true>) does not run.  The tile is the one conv_plan's cost model picks for the
+// shape (or tune_cfg forces); the epilogue exists for the tiles of kRgbReg / kRgbDma.
 namespace w2e {
-
-static bool rgbfold_launch(const ConvPlan& pl, hipStream_t s) {
-    const ConvParams& p = pl.p;
-    const int grid = (int)pl.grid;
-    if (pl.use_dma) {
-        switch (pl.cfg) {
-            case 0: launch_cfg<W2E_CONV_DOWN, EPI_DOT_RGB, 2, 4, 2, 4, 8, 1>(p, grid, pl.lds, s); return true;
-            case 9: launch_cfg<W2E_CONV_DOWN, EPI_DOT_RGB, 2, 2, 2, 4, 8, 1>(p, grid, pl.lds, s); return true;
-            case 10: launch_cfg<W2E_CONV_DOWN, EPI_DOT_RGB, 2, 2, 1, 8, 8, 1>(p, grid, pl.lds, s); return true;
-        }
-        return false;
-    }
-    switch (pl.cfg) {  // (tiles 1, 2 and 8 stage more patch elements per thread than DOWN's register prefetch holds: never picked)
-        case 0: launch_cfg<W2E_CONV_DOWN, EPI_DOT_RGB, 2, 4, 2, 4, 8>(p, grid, pl.lds, s); return true;
-        case 3: launch_cfg<W2E_CONV_DOWN, EPI_DOT_RGB, 2, 2, 2, 2, 8>(p, grid, pl.lds, s); return true;
-        case 4: launch_cfg<W2E_CONV_DOWN, EPI_DOT_RGB, 1, 4, 2, 2, 8>(p, grid, pl.lds, s); return true;
-        case 5: launch_cfg<W2E_CONV_DOWN, EPI_DOT_RGB, 1, 2, 2, 2, 8>(p, grid, pl.lds, s); return true;
-        case 6: launch_cfg<W2E_CONV_DOWN, EPI_DOT_RGB, 1, 1, 2, 2, 8>(p, grid, pl.lds, s); return true;
-        case 7: launch_cfg<W2E_CONV_DOWN, EPI_DOT_RGB, 1, 1, 4, 1, 8>(p, grid, pl.lds, s); return true;
-        case 9: launch_cfg<W2E_CONV_DOWN, EPI_DOT_RGB, 2, 2, 2, 4, 8>(p, grid, pl.lds, s); return true;
-        case 10: launch_cfg<W2E_CONV_DOWN, EPI_DOT_RGB, 2, 2, 1, 8, 8>(p, grid, pl.lds, s); return true;
-    }
-    return false;
-}
-
-static bool rgbfold_has_cfg(bool dma, int cfg) {
-    return dma ? (cfg == 0 || cfg == 9 || cfg == 10) : (cfg == 0 || (cfg >= 3 && cfg <= 7) || cfg == 9 || cfg == 10);
-}
 
 // Why the folded form cannot take a launch the dispatcher planned, or nullptr.
 static const char* rgbfold_refusal(const Options& opt, const ConvPlan& pl) {
     if (opt.deterministic) return "deterministic mode keeps the two-kernel path (the sums are joined with fp32 atomics)";
     if (opt.conv_precision != 0 || pl.use_x3) return "conv_precision = bf16x3 keeps the two-kernel path";
     if (pl.p.splits > 1) return "a split-K launch keeps the two-kernel path (the epilogue needs the complete sum)";
-    if (!rgbfold_has_cfg(pl.use_dma, pl.cfg)) return "the tile has no ToRGB-backward epilogue";
+    if (!has_tile(tile_mask(W2E_CONV_DOWN, EPI_DOT_RGB, pl.use_dma ? 1 : 0), pl.cfg)) return "the tile has no ToRGB-backward epilogue";
     return nullptr;
 }
 
@@ -1973,13 +1954,6 @@ static bool rgbfold_auto(const Options& opt, int batch, int k_ch, int n_ch, int 
     (void)batch, (void)k_ch, (void)n_ch;
     return (int64_t)h * w >= 128 * 128;
 }
-
-static int rgbfold_plan(int batch, int k_ch, int n_ch, int h, int w, bool quiet, ConvPlan* pl) {
-    pl->quiet = quiet;
-    // (the tile choice depends on the mode, the shape and the options alone: no tensor is looked at)
-    return conv_impl(W2E_CONV_DOWN, nullptr, nullptr, nullptr, nullptr, nullptr, batch, k_ch, n_ch, h, w, 0, nullptr, nullptr, nullptr, nullptr,
-                     nullptr, nullptr, 0, 0, nullptr, pl);
-}
 }  // namespace w2e
 
 extern "C" int w2e_modconv_down_rgbfold_plan(int batch, int k_ch, int n_ch, int h, int w, int* fold) {
@@ -1988,8 +1962,8 @@ extern "C" int w2e_modconv_down_rgbfold_plan(int batch, int k_ch, int n_ch, int 
     *fold = 0;
     if (opt.tune_rgbfold == 0 || batch <= 0 || k_ch <= 0 || n_ch <= 0 || h <= 0 || w <= 0) return 0;
     if (opt.tune_rgbfold < 0 && !rgbfold_auto(opt, batch, k_ch, n_ch, h, w)) return 0;
-    ConvPlan pl{};
-    if (rgbfold_plan(batch, k_ch, n_ch, h, w, true, &pl) != 0) return 0;  // (e.g. a forced tile that does not fit: the caller's ordinary launch reports it)
+    ConvPlan pl;
+    if (conv_plan(W2E_CONV_DOWN, batch, k_ch, n_ch, h, w, 0, 0, opt, &pl) != 0) return 0;  // (e.g. a forced tile that does not fit: the caller's ordinary launch reports it)
     *fold = rgbfold_refusal(opt, pl) ? 0 : 1;
     return 0;
 }
@@ -2003,9 +1977,10 @@ extern "C" int w2e_modconv_down_rgbfold(const float* x, const float* wp, const f
     W2E_REQUIRE(gain > 0.f && slope > 0.f, "modconv_down_rgbfold: gain and slope must be positive");
     if (batch == 0) return 0;
     const Options& opt = options();
-    ConvPlan pl{};
-    const int rc = rgbfold_plan(batch, k_ch, n_ch, h, w, false, &pl);
+    ConvPlan pl;
+    int rc = conv_plan(W2E_CONV_DOWN, batch, k_ch, n_ch, h, w, 0, 0, opt, &pl);
     if (rc != 0) return rc;
+    if (opt.tune_print) conv_print(pl, EPI_DOT_RGB);  // the layer line, as for any conv launch
     const char* why = rgbfold_refusal(opt, pl);
     W2E_REQUIRE(!why, "modconv_down_rgbfold: %s (K %d N %d %dx%d B %d, cfg %d)", why, k_ch, n_ch, h, w, batch, pl.cfg);
     W2E_REQUIRE((int64_t)3 * h * w * 4 < ((int64_t)1 << 31), "modconv_down_rgbfold: one image of the RGB gradient exceeds 2 GB");
@@ -2016,7 +1991,8 @@ extern "C" int w2e_modconv_down_rgbfold(const float* x, const float* wp, const f
     if (opt.tune_print)  // (a line of its own format after the layer line: the census of tests/test_gpu_rgbfold.py keys on it)
         fprintf(stderr, "modconv rgbfold variant cfg %d dma %d styled %d noise %d K %d N %d %dx%d B %d\n", pl.cfg, pl.use_dma ? 1 : 0,
                 style ? 1 : 0, noise ? 1 : 0, k_ch, n_ch, h, w, batch);
-    W2E_REQUIRE(rgbfold_launch(pl, (hipStream_t)stream), "modconv_down_rgbfold: internal: configuration %d not instantiated", pl.cfg);
+    rc = launch_plan(pl, p, EPI_DOT_RGB, (hipStream_t)stream);
+    if (rc != 0) return rc;
     W2E_LAUNCH_CHECK("modconv_down_rgbfold");
     return 0;
 }
