@@ -100,9 +100,11 @@ def test_fixture_run_takes_the_fused_path_and_matches_the_reference(fused_calls)
         for p, gr in zip(params, grads):
             p.grad = gr.to(DEV)
         before = [p.grad.clone() for p in params]
+        versions = [p._version for p in params]
         opt.step()
         ref.step(grads)
         assert len(fused_calls) == it + 1 and fused_calls[-1] == len(params), "the fused path was not taken"
+        assert all(p._version > v for p, v in zip(params, versions)), "an in-place update must bump the parameter's version (caches key on it)"
         for (n, _), p, b in zip(RANGER_SHAPES, params, before):
             assert torch.equal(p.grad, b), f"step {it}: p.grad of {n} was modified"
             assert_close(p, g[f"step{it}.{n}"], TOL, f"step {it} {n}")
@@ -193,3 +195,28 @@ def test_extra_shapes_match_float64(fused_calls, shape):
         assert_close(params[0], ref.p[0], TOL, f"{shape} step {it}")
     assert len(fused_calls) == 7
     _hold_state(opt, params, ref, f"{shape}")
+
+
+def test_a_fused_step_does_not_leave_the_frozen_path_its_primed_products(fused_calls):
+    """EqualLinear under no_grad serves cached weight*scale / bias*lr_mul products (the mapper's stock path reads them): a validation
+    pass primes them, a fused step writes the parameters through raw pointers, and the next validation pass must see the new ones."""
+    from where2edit_amd.op import fused_leaky_relu
+    from where2edit_amd.ranger import Ranger
+    from where2edit_amd.stylegan2 import EqualLinear
+    lin = EqualLinear(8, 8, lr_mul=0.01, activation="fused_lrelu")
+    with torch.no_grad():
+        lin.weight.copy_(seeded.tensor("ranger.stale.w", (8, 8)) / 0.01)
+        lin.bias.copy_(seeded.tensor("ranger.stale.b", (8,)))
+    lin = lin.to(DEV)
+    x = seeded.tensor("ranger.stale.x", (2, 8)).to(DEV)
+    with torch.no_grad():
+        primed = lin(x).clone()
+    lin.weight.grad = seeded.tensor("ranger.stale.gw", (8, 8)).to(DEV)
+    lin.bias.grad = seeded.tensor("ranger.stale.gb", (8,)).to(DEV)
+    Ranger(lin.parameters(), lr=LR).step()
+    assert fused_calls == [2], "the kernel was not taken"
+    with torch.no_grad():
+        after = lin(x)
+        live = fused_leaky_relu(torch.nn.functional.linear(x, lin.weight * lin.scale), lin.bias * lin.lr_mul)
+    assert torch.equal(after, live), "the no_grad forward did not use the live parameters"
+    assert not torch.equal(after, primed), "the step did not change the output: the test shows nothing"

@@ -12,7 +12,9 @@ Layout:
   clip_vit.py, clip_loss.py                criteria/clip_loss.py surface + ViT-B/32
   id_loss.py, irse_hip.py                  criteria/id_loss.py surface + IR-SE50 on the conv engine
   perceptual_loss.py                       criteria/perceptual_loss.py surface: VGG16 relu2_2 MSE on the conv engine
+  derived.py              the one cache of tensors derived from frozen parameters, and invalidate (= stylegan2.invalidate_caches)
   coach.py, ranger.py     the mapper training step (mapper/training/coach.py:70-92) + optimizer
+  _fused_opt.py           what Ranger and Adam share around their one-launch kernels (csrc/multi_tensor.h on the C side)
   run_attention.py, region_style_hip.py, adam.py   the region-attention net and its training step (attention/run_attention.py): the
                           style branch as one node on csrc/region_style.hip, `Adam` = torch.optim.Adam's rule as one launch
   dist.py                 data-parallel step: shard latents, one RCCL all-reduce of mapper grads

@@ -6,13 +6,16 @@ tensors on one GPU.  Everything else (CPU tensors, other dtypes, strided gradien
 updates, the operations of torch's own single-tensor form in the same order.  The optimizer of the region-attention loop
 (attention/run_attention.py:1051); works under `GradScaler.step` unchanged (it has no `_step_supports_amp_scaling`: the scaler
 unscales, checks and calls `step()` or skips it)."""
-import ctypes
-
 import torch
 from torch.optim.optimizer import Optimizer
 
+from ._fused_opt import FusedStep
 
-class Adam(Optimizer):
+
+class Adam(FusedStep, Optimizer):
+    _fused_entry = "w2e_adam_step"
+    _fused_state = ("exp_avg", "exp_avg_sq")
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, maximize=False, fused=None):
         """`fused`: None = the one-launch kernel wherever it applies, False = never, True = raise where it does not apply."""
         if amsgrad:
@@ -34,26 +37,6 @@ class Adam(Optimizer):
         super().__init__(params, defaults)
         self.fused = fused
 
-    def _fused_applies(self, params):
-        """Every parameter, gradient and state tensor of the list a contiguous fp32 tensor on one GPU, and the library there."""
-        if self.fused is False:
-            return False
-        dev = params[0].device
-        ok = dev.type == "cuda"
-        for p in params:
-            st = self.state[p]
-            for t in (p, p.grad, st["exp_avg"], st["exp_avg_sq"]):
-                ok = ok and t.device == dev and t.dtype == torch.float32 and t.is_contiguous() and t.numel() < 2 ** 31
-        if ok:
-            try:
-                from . import _lib
-                _lib.load()
-            except (RuntimeError, OSError):
-                ok = False
-        if not ok and self.fused:
-            raise RuntimeError("Adam(fused=True): needs contiguous fp32 parameters, gradients and state on one GPU, and libw2e.so")
-        return ok
-
     @staticmethod
     def _scalars(group, step):
         """adam.py (_single_tensor_adam): step_size = lr / (1 - beta1^step), bias_correction2_sqrt = sqrt(1 - beta2^step)."""
@@ -61,21 +44,10 @@ class Adam(Optimizer):
         return group["lr"] / (1 - beta1 ** step), (1 - beta2 ** step) ** 0.5
 
     def _fused_update(self, group, step, params):
-        from . import _lib
         beta1, beta2 = group["betas"]
         step_size, bc2_sqrt = self._scalars(group, step)
-        with torch.cuda.device(params[0].device):
-            for at in range(0, len(params), 64):  # the kernel's table holds 64 tensors: one launch per 64
-                chunk = params[at:at + 64]
-                n = len(chunk)
-                ptrs = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])  # noqa: E731,B023
-                state = [self.state[p] for p in chunk]
-                _lib.call("w2e_adam_step", n, ptrs(chunk), ptrs([p.grad for p in chunk]), ptrs([s["exp_avg"] for s in state]),
-                          ptrs([s["exp_avg_sq"] for s in state]), (ctypes.c_int64 * n)(*[p.numel() for p in chunk]), float(beta1), float(beta2),
-                          float(group["eps"]), float(step_size), float(bc2_sqrt), float(group["weight_decay"]), _lib.stream_ptr())
-                # the kernel wrote through raw pointers: tell autograd (and every cache keyed on `_version`, such as the
-                # region-attention net's scaled-weight caches) that these tensors changed in place
-                torch.autograd.graph.increment_version(chunk)
+        self._fused_call(params, (torch.Tensor.numel,), (float(beta1), float(beta2), float(group["eps"]), float(step_size),
+                                                          float(bc2_sqrt), float(group["weight_decay"])))
 
     @torch.no_grad()
     def step(self, closure=None):

@@ -2,25 +2,16 @@
 // the region-attention loop (attention/run_attention.py:1051, :1419).  As multi-tensor ops it is a dozen passes that each re-read
 // their lists of about 110 tensors; here every element of p, grad, exp_avg and exp_avg_sq is read once and p, exp_avg, exp_avg_sq
 // are written once.  The bias corrections and the step size are host arithmetic: the host passes the finished scalars.  A wave owns
-// 1024 consecutive elements of one tensor; the tensors travel as a table in the kernel arguments, AD_MAXT per launch (csrc/ranger.hip
-// is the same scheme).
+// 1024 consecutive elements of one tensor; the tensors travel as a table in the kernel arguments (multi_tensor.h).
 #include "common.h"
 #include "device.h"
+#include "multi_tensor.h"
 
 namespace w2e {
 
-constexpr int AD_MAXT = 64;     // tensors per launch: 64 x 40 bytes of table stay inside the 4 KB of kernel arguments
 constexpr int AD_CHUNK = 1024;  // elements per wave
 
-struct AdamTable {
-    float* p[AD_MAXT];
-    const float* g[AD_MAXT];
-    float* m[AD_MAXT];     // exp_avg
-    float* v[AD_MAXT];     // exp_avg_sq
-    int n[AD_MAXT];        // elements
-    int first[AD_MAXT];    // index of the tensor's first unit
-    int count, units;
-};
+struct AdamTable : MultiTensorTable {};  // no extra column: 64 x 40 bytes + the two counts of the 4 KB of kernel arguments
 
 struct AdamScalars {
     float beta1, beta2, omb1, omb2, eps, step_size, bc2_sqrt, weight_decay;  // omb = 1 - beta, rounded from the host's double
@@ -30,8 +21,7 @@ __global__ __launch_bounds__(256) void adam_step_kernel(AdamTable tb, AdamScalar
     const int lane = threadIdx.x & 63;
     const int unit = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
     if (unit >= tb.units) return;
-    int t = 0;
-    while (t + 1 < tb.count && unit >= tb.first[t + 1]) ++t;
+    const int t = mt_tensor_of(tb, unit);
     const int64_t base = (int64_t)(unit - tb.first[t]) * AD_CHUNK;
     const int64_t left = (int64_t)tb.n[t] - base;
     const int len = left < AD_CHUNK ? (int)left : AD_CHUNK;
@@ -65,22 +55,13 @@ extern "C" int w2e_adam_step(int count, float* const* p, const float* const* gra
     }
     const AdamScalars sc{(float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)step_size,
                          (float)bias_correction2_sqrt, (float)weight_decay};
-    for (int at = 0; at < count; at += AD_MAXT) {  // AD_MAXT tensors per launch (empty ones included: they own no unit)
-        AdamTable tb{};
-        int64_t units = 0;
-        const int end = at + AD_MAXT < count ? at + AD_MAXT : count;
-        for (int i = at; i < end; ++i) {
-            if (numel[i] == 0) continue;
-            const int k = tb.count++;
-            tb.p[k] = p[i], tb.g[k] = grad[i], tb.m[k] = exp_avg[i], tb.v[k] = exp_avg_sq[i];
-            tb.n[k] = (int)numel[i], tb.first[k] = (int)units;
-            units += ceil_div(numel[i], AD_CHUNK);
-        }
-        if (tb.count == 0) continue;
-        W2E_REQUIRE(units <= INT32_MAX, "adam_step: too many elements in one launch");
-        tb.units = (int)units;
-        adam_step_kernel<<<(unsigned)ceil_div(units, 4), 256, 0, (hipStream_t)stream>>>(tb, sc);
-        W2E_LAUNCH_CHECK("adam_step");
-    }
-    return 0;
+    const int rc = mt_for_each_table<AdamTable>(
+        count, p, grad, exp_avg, exp_avg_sq, numel, [&](int i) { return ceil_div(numel[i], AD_CHUNK); }, [](AdamTable&, int, int) {},
+        [&](const AdamTable& tb) {
+            adam_step_kernel<<<(unsigned)ceil_div(tb.units, 4), 256, 0, (hipStream_t)stream>>>(tb, sc);
+            W2E_LAUNCH_CHECK("adam_step");
+            return 0;
+        });
+    W2E_REQUIRE(rc >= 0, "adam_step: tensor %d has too many elements for one launch", -1 - rc);
+    return rc;
 }

@@ -6,26 +6,19 @@
 // The rectification, the step size and the look-ahead period are host control flow (ranger.py:124-161): the host passes the
 // finished scalars.  A wave owns one "unit": a row (all dimensions but the first) of a tensor that is centralised -- the row's mean is
 // a wave_sum, the centralised gradient lives in registers only and p.grad is never written -- or 1024 consecutive elements of a tensor
-// that is not.  The tensors travel as a table in the kernel arguments, RG_MAXT per launch.
+// that is not.  The tensors travel as a table in the kernel arguments (multi_tensor.h).
 #include "common.h"
 #include "device.h"
+#include "multi_tensor.h"
 
 namespace w2e {
 
-constexpr int RG_MAXT = 64;          // tensors per launch: 64 x 52 bytes of table stay inside the 4 KB of kernel arguments
 constexpr int RG_REGS = 16;          // gradient elements a lane keeps: rows up to 64 * 16 = 1024 elements are read once
 constexpr int RG_CHUNK = 64 * RG_REGS;
 
-struct RangerTable {
-    float* p[RG_MAXT];
-    const float* g[RG_MAXT];
-    float* m[RG_MAXT];       // exp_avg
-    float* v[RG_MAXT];       // exp_avg_sq
-    float* slow[RG_MAXT];    // slow_buffer (look-ahead steps only)
-    int n[RG_MAXT];          // elements
-    int row[RG_MAXT];        // row length for the centralisation, 0 = none
-    int first[RG_MAXT];      // index of the tensor's first unit
-    int count, units;
+struct RangerTable : MultiTensorTable {   // 64 x 52 bytes + the two counts: 3336 of the 4 KB of kernel arguments, 44 more for the scalars
+    float* slow[MT_MAXT];    // slow_buffer (look-ahead steps only)
+    int row[MT_MAXT];        // row length for the centralisation, 0 = none
 };
 
 struct RangerScalars {
@@ -38,8 +31,7 @@ __global__ __launch_bounds__(256) void ranger_step_kernel(RangerTable tb, Ranger
     const int lane = threadIdx.x & 63;
     const int unit = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
     if (unit >= tb.units) return;
-    int t = 0;
-    while (t + 1 < tb.count && unit >= tb.first[t + 1]) ++t;
+    const int t = mt_tensor_of(tb, unit);
     const int u = unit - tb.first[t], row = tb.row[t];
     const int64_t base = row ? (int64_t)u * row : (int64_t)u * RG_CHUNK;
     const int64_t left = (int64_t)tb.n[t] - base;
@@ -102,26 +94,15 @@ extern "C" int w2e_ranger_step(int count, float* const* p, const float* const* g
     }
     RangerScalars sc{(float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)neg_step_size, (float)decay,
                      (float)alpha, rectified != 0, decay != 1.0, lookahead != 0};
-    int at = 0;
-    while (at < count) {  // RG_MAXT tensors per launch
-        RangerTable tb{};
-        int64_t units = 0;
-        for (; at < count && tb.count < RG_MAXT; ++at) {
-            if (numel[at] == 0) continue;
-            const int64_t mine = row_len[at] ? numel[at] / row_len[at] : ceil_div(numel[at], RG_CHUNK);
-            if (units + mine > INT32_MAX) {
-                W2E_REQUIRE(tb.count > 0, "ranger_step: tensor %d has too many rows", at);
-                break;  // the next launch takes it
-            }
-            const int k = tb.count++;
-            tb.p[k] = p[at], tb.g[k] = grad[at], tb.m[k] = exp_avg[at], tb.v[k] = exp_avg_sq[at], tb.slow[k] = lookahead ? slow_buffer[at] : nullptr;
-            tb.n[k] = (int)numel[at], tb.row[k] = (int)row_len[at], tb.first[k] = (int)units;
-            units += mine;
-        }
-        if (tb.count == 0) continue;
-        tb.units = (int)units;
-        ranger_step_kernel<<<(unsigned)ceil_div(units, 4), 256, 0, (hipStream_t)stream>>>(tb, sc);
-        W2E_LAUNCH_CHECK("ranger_step");
-    }
-    return 0;
+    const int rc = mt_for_each_table<RangerTable>(
+        count, p, grad, exp_avg, exp_avg_sq, numel,
+        [&](int i) { return row_len[i] ? numel[i] / row_len[i] : ceil_div(numel[i], RG_CHUNK); },
+        [&](RangerTable& tb, int k, int i) { tb.slow[k] = lookahead ? slow_buffer[i] : nullptr, tb.row[k] = (int)row_len[i]; },
+        [&](const RangerTable& tb) {
+            ranger_step_kernel<<<(unsigned)ceil_div(tb.units, 4), 256, 0, (hipStream_t)stream>>>(tb, sc);
+            W2E_LAUNCH_CHECK("ranger_step");
+            return 0;
+        });
+    W2E_REQUIRE(rc >= 0, "ranger_step: tensor %d has too many rows", -1 - rc);
+    return rc;
 }

@@ -41,6 +41,7 @@ from . import _lib
 from . import functional as K
 from . import irse_hip as IR
 from ._lib import call, ptr, stream_ptr
+from .derived import derived
 
 SQRT2 = math.sqrt(2.0)
 SLOPE = 0.2
@@ -318,14 +319,10 @@ def _live(*params):
 
 def _cached(mod, params, derive):
     """Packed weights of `mod`: derived in every forward while a parameter is trained (graph replays and optimizer steps then see the
-    live weights), else cached on (data_ptr, _version) under the attribute stylegan2.invalidate_caches clears."""
+    live weights), else cached (derived.py)."""
     if _live(*params):
         return derive()
-    key = tuple((q.data_ptr(), q._version, q.device) for q in params)
-    if getattr(mod, "_cache_key", None) != key:
-        mod._cache = derive()
-        mod._cache_key = key
-    return mod._cache
+    return derived(mod, "_cache", params, derive)
 
 
 def resblock_plan(block):

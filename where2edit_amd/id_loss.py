@@ -99,11 +99,9 @@ class Backbone(Module):
         (irse_hip.backbone_forward).  Otherwise -- CPU tensors, train mode, trainable weights -- the stock module tree."""
         if x.is_cuda and not self.training and x.dtype == torch.float32 and not any(p.requires_grad for p in self.parameters()):
             from . import irse_hip
-            key = tuple((p.data_ptr(), p._version) for p in self.parameters())
-            if getattr(self, "_plan_key", None) != key:
-                self._plan = irse_hip.BackbonePlan(self)
-                self._plan_key = key
-            return irse_hip.backbone_forward(self._plan, x, n_grad)
+            from .derived import derived
+            plan = derived(self, "_plan", list(self.parameters()), lambda: irse_hip.BackbonePlan(self))
+            return irse_hip.backbone_forward(plan, x, n_grad)
         if x.is_cuda and not getattr(self, "_warned_stock", False):
             import warnings
             warnings.warn("IR-SE50 Backbone is running on stock PyTorch ops (train mode or trainable weights): the HIP path needs "

@@ -13,6 +13,7 @@ from torch.autograd.function import once_differentiable
 from . import _lib
 from . import functional as K
 from ._lib import call, ptr, stream_ptr
+from .derived import Holder, derived, drop
 
 _I = __import__("ctypes").c_int
 _P = __import__("ctypes").c_void_p
@@ -188,19 +189,14 @@ class UnitPlan:
         return gpool
 
 
-_REP = {}
+_REP = Holder()
 
 
 def _rep(v, batch):
     """[C] -> [batch, C] (the conv engine takes per-sample scales); cached: the vectors are frozen parameters."""
-    key = (v.data_ptr(), v._version, batch)
-    hit = _REP.get(key)
-    if hit is None or hit[0] is not v:
-        if len(_REP) > 4096:
-            _REP.clear()
-        hit = (v, v.unsqueeze(0).expand(batch, -1).contiguous())
-        _REP[key] = hit
-    return hit[1]
+    if len(_REP.__dict__.get("_rep", ())) > 4096:
+        drop(_REP)
+    return derived(_REP, ("_rep", id(v), batch), (v,), lambda: v.unsqueeze(0).expand(batch, -1).contiguous())
 
 
 class _IRUnit(torch.autograd.Function):

@@ -28,6 +28,7 @@ from torch.autograd.function import once_differentiable
 from . import functional as K
 from . import irse_hip as IR
 from ._lib import call, ptr, stream_ptr
+from .derived import derived
 
 VggOutputs = namedtuple("VggOutputs", ["relu1_2", "relu2_2", "relu3_3", "relu4_3"])
 
@@ -257,12 +258,8 @@ class Vgg16(torch.nn.Module):
                 param.requires_grad = False
 
     def plan(self):
-        """The packed parameters, rebuilt when a weight changes (load_state_dict, .to)."""
-        key = tuple((p.data_ptr(), p._version, p.device) for p in self.parameters())
-        if getattr(self, "_plan_key", None) != key:
-            self._plan = _Plan(self)
-            self._plan_key = key
-        return self._plan
+        """The packed parameters (cached: derived.py)."""
+        return derived(self, "_plan", list(self.parameters()), lambda: _Plan(self))
 
     def forward(self, X):
         _refuse_trainable(self)

@@ -17,6 +17,7 @@ from torch import nn
 from torch.nn import BatchNorm2d, Conv2d, Module, PReLU, Sequential
 from torch.nn import functional as F
 
+from .derived import derived
 from .id_loss import bottleneck_IR, bottleneck_IR_SE, get_blocks
 from .stylegan2 import EqualLinear
 
@@ -78,14 +79,14 @@ class GradualStyleBlock(Module):
 
     def _packs(self):
         from . import functional as K
-        key = tuple((p.data_ptr(), p._version) for p in self.convs.parameters())
-        if getattr(self, "_pack_key", None) != key:
+
+        def build():
             with torch.no_grad():
-                self._pack = [(K.conv_pack(m.weight.detach().float(), 1.0, False, False), m.bias.detach().float().contiguous(),
-                               torch.full((m.weight.shape[0],), m_act.negative_slope, device=m.weight.device))
-                              for m, m_act in zip(self.convs[0::2], self.convs[1::2])]
-            self._pack_key = key
-        return self._pack
+                return [(K.conv_pack(m.weight.detach().float(), 1.0, False, False), m.bias.detach().float().contiguous(),
+                         torch.full((m.weight.shape[0],), m_act.negative_slope, device=m.weight.device))
+                        for m, m_act in zip(self.convs[0::2], self.convs[1::2])]
+
+        return derived(self, "_pack", list(self.convs.parameters()), build)
 
     def forward(self, x):
         if self._hip_ok(x):
@@ -128,8 +129,8 @@ class _EncoderBase(Module):
         """c1, c2, c3 = the body's outputs after units 6, 20, 23 (psp_encoders.py:176-183)."""
         if self._hip(x):
             from . import irse_hip
-            key = tuple((p.data_ptr(), p._version) for n, p in self.named_parameters() if n.startswith(("input_layer", "body")))
-            if getattr(self, "_plan_key", None) != key:
+
+            def build():
                 plan = types.SimpleNamespace()
                 with torch.no_grad():
                     il = self.input_layer
@@ -140,10 +141,12 @@ class _EncoderBase(Module):
                                   "slope": il[2].weight.detach().float().contiguous()}
                     specs = [b_ for blk in get_blocks(len_to_layers(len(self.body))) for b_ in blk]
                     plan.units = [irse_hip.UnitPlan(u, s.in_channel, s.depth, s.stride) for u, s in zip(self.body, specs)]
-                self._plan, self._plan_key = plan, key
-            y = irse_hip._InputLayer.apply(x, self._plan.input, None)
+                return plan
+
+            plan = derived(self, "_plan", [p for n, p in self.named_parameters() if n.startswith(("input_layer", "body"))], build)
+            y = irse_hip._InputLayer.apply(x, plan.input, None)
             taps = {}
-            for i, u in enumerate(self._plan.units):
+            for i, u in enumerate(plan.units):
                 y = irse_hip._IRUnit.apply(y, u, None)
                 if i in (6, 20, 23):
                     taps[i] = y
@@ -161,13 +164,13 @@ class _EncoderBase(Module):
         if x.is_cuda and not torch.is_grad_enabled():
             from . import functional as K
             from . import irse_hip
-            key = (conv.weight.data_ptr(), conv.weight._version, conv.bias.data_ptr(), conv.bias._version)
-            cache = self.__dict__.setdefault("_lat", {})
-            if cache.get(id(conv), (None,))[0] != key:
+
+            def build():
                 w9 = torch.zeros(conv.weight.shape[0], conv.weight.shape[1], 3, 3, device=x.device)
                 w9[:, :, 1, 1] = conv.weight.detach()[:, :, 0, 0]
-                cache[id(conv)] = (key, K.conv_pack(w9, 1.0, False, False), conv.bias.detach().float().contiguous())
-            _, wp, bias = cache[id(conv)]
+                return K.conv_pack(w9, 1.0, False, False), conv.bias.detach().float().contiguous()
+
+            wp, bias = derived(conv, "_lat", (conv.weight, conv.bias), build)
             return irse_hip.conv3x3(x.contiguous(), wp, conv.weight.shape[0], x.shape[2], x.shape[3], bias=bias)
         return conv(x)
 

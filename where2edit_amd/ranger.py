@@ -6,14 +6,18 @@ the per-element update of every parameter at the same `step` is ONE launch of li
 (csrc/ranger.hip) when all its tensors are contiguous fp32 tensors on one GPU.  Everything else (CPU
 tensors, other dtypes, strided gradients) takes multi-tensor (`torch._foreach_*`) updates instead of the
 reference's Python loop of ~10 tiny ops per parameter."""
-import ctypes
 import math
 
 import torch
 from torch.optim.optimizer import Optimizer
 
+from ._fused_opt import FusedStep
 
-class Ranger(Optimizer):
+
+class Ranger(FusedStep, Optimizer):
+    _fused_entry = "w2e_ranger_step"
+    _fused_state = ("exp_avg", "exp_avg_sq", "slow_buffer")
+
     def __init__(self, params, lr=1e-3, alpha=0.5, k=6, N_sma_threshhold=5, betas=(.95, 0.999), eps=1e-5,
                  weight_decay=0, use_gc=True, gc_conv_only=False, fused=None):
         """`fused`: None = the one-launch kernel wherever it applies, False = never, True = raise where it does not apply."""
@@ -35,42 +39,19 @@ class Ranger(Optimizer):
         self.gc_gradient_threshold = 3 if gc_conv_only else 1
         self.fused = fused
 
-    def _fused_applies(self, params):
-        """Every parameter, gradient and state tensor of the list a contiguous fp32 tensor on one GPU, and the library there."""
-        if self.fused is False:
-            return False
-        dev = params[0].device
-        ok = dev.type == "cuda"
-        for p in params:
-            st = self.state[p]
-            for t in (p, p.grad, st["exp_avg"], st["exp_avg_sq"], st["slow_buffer"]):
-                ok = ok and t.device == dev and t.dtype == torch.float32 and t.is_contiguous() and t.numel() < 2 ** 31
-        if ok:
-            try:
-                from . import _lib
-                _lib.load()
-            except (RuntimeError, OSError):
-                ok = False
-        if not ok and self.fused:
-            raise RuntimeError("Ranger(fused=True): needs contiguous fp32 parameters, gradients and state on one GPU, and libw2e.so")
-        return ok
-
     def _fused_update(self, group, step, params):
         """ranger.py:104-161 for the parameters at `step` as one w2e_ranger_step call: the same scalars as the multi-tensor path below."""
-        from . import _lib
         beta1, beta2 = group["betas"]
         n_sma, step_size = self._radam_step_size(step, beta1, beta2, self.N_sma_threshhold)
-        n = len(params)
-        ptrs = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])  # noqa: E731
-        state = [self.state[p] for p in params]
-        rows = [p.numel() // p.shape[0] if self.use_gc and p.dim() > self.gc_gradient_threshold and p.numel() else 0 for p in params]
-        with torch.cuda.device(params[0].device):
-            _lib.call("w2e_ranger_step", n, ptrs(params), ptrs([p.grad for p in params]), ptrs([s["exp_avg"] for s in state]),
-                      ptrs([s["exp_avg_sq"] for s in state]), ptrs([s["slow_buffer"] for s in state]),
-                      (ctypes.c_int64 * n)(*[p.numel() for p in params]), (ctypes.c_int64 * n)(*rows), float(beta1), float(beta2),
-                      float(group["eps"]), float(-step_size * group["lr"]), int(n_sma > self.N_sma_threshhold),
-                      float(1 - group["weight_decay"] * group["lr"]) if group["weight_decay"] != 0 else 1.0,
-                      int(step % group["k"] == 0), float(self.alpha), _lib.stream_ptr())
+
+        def row(p):  # the centralised row's length (all dimensions but the first), 0 = not centralised
+            return p.numel() // p.shape[0] if self.use_gc and p.dim() > self.gc_gradient_threshold and p.numel() else 0
+
+        self._fused_call(params, (torch.Tensor.numel, row),
+                         (float(beta1), float(beta2), float(group["eps"]), float(-step_size * group["lr"]),
+                          int(n_sma > self.N_sma_threshhold),
+                          float(1 - group["weight_decay"] * group["lr"]) if group["weight_decay"] != 0 else 1.0,
+                          int(step % group["k"] == 0), float(self.alpha)))
 
     @staticmethod
     def _radam_step_size(step, beta1, beta2, threshold):

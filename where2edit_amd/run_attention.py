@@ -32,6 +32,7 @@ from torch.nn import functional as F
 
 from . import _lib
 from ._lib import call, ptr, stream_ptr
+from .derived import derived
 from .stylegan2 import EqualLinear, StyledConv
 
 _I32P = ctypes.c_void_p
@@ -311,28 +312,16 @@ class FullSpaceMapperFEATClusterLinStyle_Net(nn.Module):
     # ---- the mask branch -------------------------------------------------------------------------------------------
     def _noise_is_off(self, param):
         """NoiseInjection strength == 0 (its init, and -- the mask branch being frozen -- its value for the whole run):
-        answered from a cache keyed on the parameter's version, so a forward pass does not synchronise 19 times."""
-        cache = self.__dict__.setdefault("_noise_off", {})
-        key = (param.data_ptr(), param._version)
-        hit = cache.get(id(param))
-        if hit is None or hit[0] != key:
-            hit = (key, bool((param.detach() == 0).all().item()))
-            cache[id(param)] = hit
-        return hit[1]
+        answered from the cache (derived.py), so a forward pass does not synchronise 19 times."""
+        return derived(self, ("_noise_off", id(param)), (param,), lambda: bool((param.detach() == 0).all().item()))
 
     def _mask_params_frozen(self):
         return not any(p.requires_grad for n, p in self.named_parameters() if _is_mask_param(n))
 
     def _wscaled_t(self, conv):
-        """(scale * W[0,:,:,0,0])^T as a contiguous [C, 32] tensor, cached per conv until its weight changes."""
-        cache = self.__dict__.setdefault("_wsc_t", {})
+        """(scale * W[0,:,:,0,0])^T as a contiguous [C, 32] tensor, cached per conv."""
         w = conv.weight
-        key = (w.data_ptr(), w._version)
-        hit = cache.get(id(conv))
-        if hit is None or hit[0] != key:
-            hit = (key, (w.detach()[0, :, :, 0, 0] * conv.scale).t().contiguous())
-            cache[id(conv)] = hit
-        return hit[1]
+        return derived(self, ("_wsc_t", id(conv)), (w,), lambda: (w.detach()[0, :, :, 0, 0] * conv.scale).t().contiguous())
 
     def _text_styles(self, mods, attention_text):
         """[aff(attention_text) for aff in mods] (the per-source style EqualLinears, :798 / :826, and attention_textca_last) from ONE
@@ -343,9 +332,8 @@ class FullSpaceMapperFEATClusterLinStyle_Net(nn.Module):
             return None
         if torch.is_grad_enabled() and any(m.weight.requires_grad or m.bias.requires_grad for m in mods):
             return None
-        key = tuple((m.weight.data_ptr(), m.weight._version, m.bias.data_ptr(), m.bias._version) for m in mods)
-        cache = self.__dict__.get("_text_pack")
-        if cache is None or cache[0] != key:
+
+        def build():
             with torch.no_grad():
                 w = torch.cat([m.weight.detach().float() * m.scale for m in mods]).contiguous()
                 b = torch.cat([m.bias.detach().float() * m.lr_mul for m in mods]).contiguous()
@@ -355,9 +343,10 @@ class FullSpaceMapperFEATClusterLinStyle_Net(nn.Module):
                     meta.append(torch.stack([torch.zeros(cw, dtype=torch.long), torch.full((cw,), off), torch.full((cw,), cw), torch.arange(cw)], 1))
                     off += cw
                 meta = torch.cat(meta).to(device=w.device, dtype=torch.int32).contiguous()
-            cache = (key, (w, b, meta, [m.weight.shape[0] for m in mods]))
-            self.__dict__["_text_pack"] = cache
-        return K.style_affine_all(attention_text.reshape(attention_text.shape[0], 1, -1).float(), cache[1])
+            return w, b, meta, [m.weight.shape[0] for m in mods]
+
+        pack = derived(self, "_text_pack", [t for m in mods for t in (m.weight, m.bias)], build)
+        return K.style_affine_all(attention_text.reshape(attention_text.shape[0], 1, -1).float(), pack)
 
     def _sources(self, n_codes):
         """(StyledConv, style EqualLinear, feature_map index) in concat order: attention_first on the const input

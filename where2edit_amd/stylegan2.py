@@ -20,20 +20,8 @@ from torch import nn
 from torch.nn import functional as F
 
 from . import functional as K
+from .derived import derived, invalidate as invalidate_caches  # noqa: F401  (the public name INTEGRATION.md / DESIGN.md give callers)
 from .op import FusedLeakyReLU, fused_leaky_relu, upfirdn2d
-
-
-def invalidate_caches(module):
-    """Drop every derived-weight cache under `module` (packed conv weights, sum_k W^2, scaled EqualLinear / ToRGB weights,
-    the stacked style affines).  The caches are keyed on (data_ptr, Tensor._version): optimizer steps, load_state_dict and
-    any in-place op bump the version and rebuild them by themselves, but writes through `.data` (the reference Ranger's
-    `p.data.copy_`, rosinality's EMA `accumulate`) do NOT -- call this after such writes."""
-    for m in module.modules():
-        for attr in ("_cache_key", "_scaled_key", "_wsc_key", "_style_pack_key"):
-            if hasattr(m, attr):
-                setattr(m, attr, None)
-        if hasattr(m, "_text_cache"):
-            m._text_cache = None
 
 
 def _trainable_weight(mod):
@@ -177,16 +165,16 @@ class EqualLinear(nn.Module):
 
     def _scaled(self):
         """weight*scale and bias*lr_mul (model.py:151-158).  For frozen parameters (the decoder on the mapper path)
-        the products are cached until the parameters change instead of being recomputed by two kernels per call."""
+        the products are cached (derived.py) instead of being recomputed by two kernels per call."""
         w, b = self.weight, self.bias
         if torch.is_grad_enabled() and (w.requires_grad or (b is not None and b.requires_grad)):
             return w * self.scale, (b * self.lr_mul if b is not None else None)
-        key = (w.data_ptr(), w._version, None if b is None else (b.data_ptr(), b._version))
-        if getattr(self, "_scaled_key", None) != key:
+
+        def build():
             with torch.no_grad():
-                self._scaled_val = ((w * self.scale).detach(), (b * self.lr_mul).detach() if b is not None else None)
-            self._scaled_key = key
-        return self._scaled_val
+                return (w * self.scale).detach(), (b * self.lr_mul).detach() if b is not None else None
+
+        return derived(self, "_scaled_val", (w, b), build)
 
     def forward(self, input, scaled=None):
         """`scaled` = (weight*scale, bias*lr_mul) computed by the caller (latent_mappers batches those products over all
@@ -238,8 +226,6 @@ class ModulatedConv2d(nn.Module):
         self.weight = nn.Parameter(torch.randn(1, out_channel, in_channel, kernel_size, kernel_size))
         self.modulation = EqualLinear(style_dim, in_channel, bias_init=1)
         self.demodulate = demodulate
-        self._cache_key = None
-        self._cache = None
 
     def __repr__(self):
         return (f"{self.__class__.__name__}({self.in_channel}, {self.out_channel}, {self.kernel_size}, "
@@ -249,16 +235,11 @@ class ModulatedConv2d(nn.Module):
         """True for a layer opted in by train_conv_weights whose weight is trained: its derived tensors come from the live weight."""
         return getattr(self, "_train_weight", False) and self.weight.requires_grad
 
-    # ---- frozen-weight derived tensors, rebuilt whenever the parameter changes (in-place updates bump _version)
     def _derived(self):
         w = self.weight
-        if self._live():  # trained: derived in every forward, never from the (data_ptr, _version) cache (graph replays, optimizer steps)
+        if self._live():  # trained: derived in every forward, never from the cache (graph replays, optimizer steps)
             return self._derive(w)
-        key = (w.data_ptr(), w._version, w.device)
-        if self._cache_key != key:
-            self._cache = self._derive(w)
-            self._cache_key = key
-        return self._cache
+        return derived(self, "_cache", (w,), lambda: self._derive(w))
 
     def _derive(self, w):
         live = self._live()
@@ -401,13 +382,9 @@ class ToRGB(nn.Module):
         st = None
         if torch.is_grad_enabled() and w.requires_grad:
             wmod = (conv.scale * w.view(1, 3, conv.in_channel)) * style.reshape(batch, 1, conv.in_channel)
-        else:  # frozen decoder: scale*W is cached until the parameter changes, and the kernels apply the style themselves
-            key = (w.data_ptr(), w._version)
-            if getattr(self, "_wsc_key", None) != key:
-                with torch.no_grad():
-                    self._wsc = (conv.scale * w.detach().view(3, conv.in_channel)).contiguous()
-                self._wsc_key = key
-            wmod, st = self._wsc, style.reshape(batch, conv.in_channel)
+        else:  # frozen decoder: scale*W is cached, and the kernels apply the style themselves
+            wmod = derived(self, "_wsc", (w,), lambda: (conv.scale * w.detach().view(3, conv.in_channel)).contiguous())
+            st = style.reshape(batch, conv.in_channel)
         fuse_skip = skip is not None and self.upsample.kernel.shape == (4, 4) and self.upsample.factor == 2
         passed = None
         if passthrough:
@@ -511,10 +488,10 @@ class Generator(nn.Module):
         return plan
 
     def _style_pack(self, plan):
-        """All modulation affines stacked for w2e_style_affine_* (rebuilt when any of their parameters changes)."""
+        """All modulation affines stacked for w2e_style_affine_*."""
         mods = [m.conv.modulation for m, _, _, _ in plan]
-        key = tuple((m.weight.data_ptr(), m.weight._version, m.bias.data_ptr(), m.bias._version) for m in mods)
-        if getattr(self, "_style_pack_key", None) != key:
+
+        def build():
             with torch.no_grad():
                 w = torch.cat([m.weight.detach().float() * m.scale for m in mods]).contiguous()
                 b = torch.cat([m.bias.detach().float() * m.lr_mul for m in mods]).contiguous()
@@ -525,9 +502,9 @@ class Generator(nn.Module):
                                              torch.arange(cw)], 1))
                     off += cw
                 meta = torch.cat(meta).to(device=w.device, dtype=torch.int32).contiguous()
-            self._style_pack_val = (w, b, meta, [m.weight.shape[0] for m in mods])
-            self._style_pack_key = key
-        return self._style_pack_val
+            return w, b, meta, [m.weight.shape[0] for m in mods]
+
+        return derived(self, "_style_pack_val", [t for m in mods for t in (m.weight, m.bias)], build)
 
     def _batched_styles(self, latent, plan):
         """The 26 per-layer style vectors from one launch, when the modulation layers are frozen (they are on every
@@ -693,8 +670,6 @@ class ResBlock(nn.Module):
         self.conv2 = ConvLayer(in_channel, out_channel, 3, downsample=True, blur_kernel=blur_kernel)
         self.skip = ConvLayer(in_channel, out_channel, 1, downsample=True, activate=False, bias=False, blur_kernel=blur_kernel)
         self._blur = tuple(blur_kernel)
-        self._cache_key = None
-        self._cache = None
 
     def forward(self, input):
         from . import disc_hip

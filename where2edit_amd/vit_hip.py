@@ -13,6 +13,7 @@ from torch.autograd.function import once_differentiable
 from . import profiling
 from ._lib import call, ptr, stream_ptr
 from .clip_vit import patchify
+from .derived import derived
 
 
 def _c(t):
@@ -267,38 +268,28 @@ def _pad(v, q):
     return -(-v // q) * q
 
 
-class _WeightsPk:
-    """K-quad-major packed copies of the frozen Linear weights (w2e_pack_kq): `fwd(w)` for y = x W^T (contraction over W's columns),
-    `bwd(w)` for gx = gy W (contraction over W's rows: the packed form of W^T).  Built once per weight version: +2 x 340 MB for ViT-B/32."""
+def _pack_kq(w, transposed, half):
+    """The K-quad-major packed copy of a Linear weight (w2e_pack_kq): for y = x W^T (contraction over W's columns), or `transposed`,
+    for gx = gy W (contraction over W's rows: the packed form of W^T).  `half`: fp16 packs for w2e_gemm_pk_h
+    (VisionTransformer.set_precision("f16"), opt-in)."""
+    wd = w.detach()
+    n, k = (wd.shape[1], wd.shape[0]) if transposed else (wd.shape[0], wd.shape[1])  # output columns, contraction length
+    npad = _pad(n, 64)
+    if half:
+        if k % 16:
+            raise ValueError(f"fp16 tower GEMM: contraction length {k} is not a multiple of 16")
+        p = torch.empty((k // 8, npad, 8), device=w.device, dtype=torch.float16)
+        call("w2e_pack_kq_h", ptr(_c(wd)), p.data_ptr(), n, npad, k, wd.stride(0), int(transposed), stream_ptr())
+    else:
+        p = torch.empty((k // 4, npad, 4), device=w.device, dtype=torch.float32)
+        call("w2e_pack_kq", ptr(_c(wd)), ptr(p), n, npad, k, wd.stride(0), int(transposed), stream_ptr())
+    return p, n, k, npad, half
 
-    def __init__(self, half=False):
-        self.cache = {}
-        self.half = bool(half)  # opt-in: fp16 packs for w2e_gemm_pk_h (VisionTransformer.set_precision("f16"))
 
-    def _get(self, w, transposed):
-        key = (w.data_ptr(), w._version)
-        hit = self.cache.get((id(w), transposed))
-        if hit is None or hit[0] != key:
-            wd = w.detach()
-            n, k = (wd.shape[1], wd.shape[0]) if transposed else (wd.shape[0], wd.shape[1])  # output columns, contraction length
-            npad = _pad(n, 64)
-            if self.half:
-                if k % 16:
-                    raise ValueError(f"fp16 tower GEMM: contraction length {k} is not a multiple of 16")
-                p = torch.empty((k // 8, npad, 8), device=w.device, dtype=torch.float16)
-                call("w2e_pack_kq_h", ptr(_c(wd)), p.data_ptr(), n, npad, k, wd.stride(0), int(transposed), stream_ptr())
-            else:
-                p = torch.empty((k // 4, npad, 4), device=w.device, dtype=torch.float32)
-                call("w2e_pack_kq", ptr(_c(wd)), ptr(p), n, npad, k, wd.stride(0), int(transposed), stream_ptr())
-            hit = (key, (p, n, k, npad, self.half))
-            self.cache[(id(w), transposed)] = hit
-        return hit[1]
-
-    def fwd(self, w):
-        return self._get(w, False)
-
-    def bwd(self, w):
-        return self._get(w, True)
+def _pk(blk, name, w, half, transposed=False):
+    """The packed copy of block `blk`'s frozen weight `name`, built once per weight (derived.py): +2 x 340 MB for ViT-B/32 in one
+    precision.  The packs of both precisions stay resident once both were used (a captured graph may hold either): fp16 adds 2 x 170 MB."""
+    return derived(blk, ("_wpk", name, transposed, half), (w,), lambda: _pack_kq(w, transposed, half))
 
 
 _PK_SPLITS = {}
@@ -323,11 +314,11 @@ def _gemm_pk(a_packed, m, mpad, wpk):
     return c
 
 
-def _block_fwd(blk, params, pend, pbias, pres, geom, wpk, attn_entry):
+def _block_fwd(blk, params, pend, pbias, pres, geom, half, attn_entry):
     """The forward of one residual block on the M = batch*seq kernels, entered with the previous block's c_proj output still pending as
     split-K slabs (`pend` [S, M, D] + `pbias` + `pres`): reduce+LN, QKV GEMM, attention (`attn_entry`: "w2e_attn2_fwd" for the visual
     tower, "w2e_attn_causal_fwd" for the text tower), out-proj GEMM, reduce+LN, c_fc GEMM, reduce + QuickGELU pair, c_proj GEMM.
-    `params`: _block_params(blk) -- the PARAMETERS themselves (wpk's cache is keyed on their id).  Returns the new pending triple and the
+    `params`: _block_params(blk) -- the PARAMETERS themselves (the packs are cached on them); `half`: fp16 packs.  Returns the new pending triple and the
     tensors the backward needs."""
     b, l, dim, heads = geom
     m = b * l
@@ -335,17 +326,17 @@ def _block_fwd(blk, params, pend, pbias, pres, geom, wpk, attn_entry):
     dev = pend.device
     ln1_w, ln1_b, in_w, in_b, out_w, out_b, ln2_w, ln2_b, fc_w, fc_b, proj_w, proj_b = params
     xr, y1, mean1, rstd1 = _reduce_ln(pend, pbias, pres, ln1_w, ln1_b, blk.ln_1.eps, mpad=mpad)
-    qkv = _gemm_pk(y1, m, mpad, wpk.fwd(in_w))
+    qkv = _gemm_pk(y1, m, mpad, _pk(blk, "in", in_w, half))
     att = torch.empty((dim // 4, mpad, 4), device=dev, dtype=torch.float32)
     call(attn_entry, ptr(qkv), qkv.shape[0], m * 3 * dim, ptr(in_b), ptr(att), b, l, heads, mpad, stream_ptr())
-    o = _gemm_pk(att, m, mpad, wpk.fwd(out_w))
+    o = _gemm_pk(att, m, mpad, _pk(blk, "out", out_w, half))
     x_mid, y2, mean2, rstd2 = _reduce_ln(o, out_b, xr, ln2_w, ln2_b, blk.ln_2.eps, mpad=mpad)
-    hp = _gemm_pk(y2, m, mpad, wpk.fwd(fc_w))
+    hp = _gemm_pk(y2, m, mpad, _pk(blk, "fc", fc_w, half))
     n_fc = fc_w.shape[0]
     h = torch.empty((m, n_fc), device=dev, dtype=torch.float32)
     g = torch.empty((n_fc // 4, mpad, 4), device=dev, dtype=torch.float32)
     call("w2e_reduce_gelu", ptr(hp), hp.shape[0], m * n_fc, ptr(fc_b), None, ptr(h), ptr(g), m, n_fc, 0, mpad, stream_ptr())
-    pend = _gemm_pk(g, m, mpad, wpk.fwd(proj_w))
+    pend = _gemm_pk(g, m, mpad, _pk(blk, "proj", proj_w, half))
     return (pend, proj_b, x_mid), (xr, mean1, rstd1, qkv, x_mid, mean2, rstd2, h)
 
 
@@ -357,7 +348,7 @@ class _TransformerV3(torch.autograd.Function):
     once; split-K slabs are summed by their consumers in a fixed order, never added atomically."""
 
     @staticmethod
-    def forward(ctx, x, heads, wpk, blocks):
+    def forward(ctx, x, heads, half, blocks):
         b, l, dim = x.shape
         m = b * l
         x2 = _c(x).reshape(m, dim)
@@ -366,11 +357,11 @@ class _TransformerV3(torch.autograd.Function):
         for blk in blocks:
             p = _block_params(blk)
             _frozen(*p)
-            (pend, pbias, pres), blk_saved = _block_fwd(blk, p, pend, pbias, pres, (b, l, dim, heads), wpk, "w2e_attn2_fwd")
+            (pend, pbias, pres), blk_saved = _block_fwd(blk, p, pend, pbias, pres, (b, l, dim, heads), half, "w2e_attn2_fwd")
             saved.append(blk_saved)
         out, _, _, _ = _reduce_ln(pend, pbias, pres, None, None, 0.0, want_y=False)
         ctx.save_for_backward(*[t for blk_saved in saved for t in blk_saved])
-        ctx.blocks, ctx.wpk, ctx.geom = blocks, wpk, (b, l, dim, heads)
+        ctx.blocks, ctx.half, ctx.geom = blocks, half, (b, l, dim, heads)
         return out.reshape(b, l, dim)
 
     @staticmethod
@@ -379,7 +370,7 @@ class _TransformerV3(torch.autograd.Function):
         b, l, dim, heads = ctx.geom
         m = b * l
         mpad = _pad(m, 32)
-        wpk = ctx.wpk
+        half = ctx.half
         g = _c(gout).reshape(m, dim)
         dev = g.device
         gp = torch.empty((dim // 4, mpad, 4), device=dev, dtype=torch.float32)  # the one stand-alone packing pass of a step
@@ -389,16 +380,16 @@ class _TransformerV3(torch.autograd.Function):
         for blk, (xr, mean1, rstd1, qkv, x_mid, mean2, rstd2, h) in zip(reversed(ctx.blocks), reversed(saved)):
             ln1_w, _, in_w, in_b, out_w, _, ln2_w, _, fc_w, _, proj_w, _ = _block_params(blk)
             n_fc = fc_w.shape[0]
-            ghp = _gemm_pk(gp, m, mpad, wpk.bwd(proj_w))                                  # through c_proj ...
+            ghp = _gemm_pk(gp, m, mpad, _pk(blk, "proj", proj_w, half, True))                                  # through c_proj ...
             gh = torch.empty((n_fc // 4, mpad, 4), device=dev, dtype=torch.float32)
             call("w2e_reduce_gelu", ptr(ghp), ghp.shape[0], m * n_fc, None, ptr(h), ptr(gh), None, m, n_fc, 1, mpad, stream_ptr())  # ... and QuickGELU'
-            gy2 = _gemm_pk(gh, m, mpad, wpk.bwd(fc_w))
+            gy2 = _gemm_pk(gh, m, mpad, _pk(blk, "fc", fc_w, half, True))
             g_mid, g_mid_p = _ln_bwd_part(gy2, x_mid, ln2_w, mean2, rstd2, g, mpad=mpad)   # through ln_2, + the residual branch
-            ga = _gemm_pk(g_mid_p, m, mpad, wpk.bwd(out_w))
+            ga = _gemm_pk(g_mid_p, m, mpad, _pk(blk, "out", out_w, half, True))
             gqkv = torch.empty((3 * dim // 4, mpad, 4), device=dev, dtype=torch.float32)
             call("w2e_attn2_bwd", ptr(qkv), qkv.shape[0], m * 3 * dim, ptr(in_b), ptr(ga), ga.shape[0], m * dim, ptr(gqkv), b, l, heads,
                  mpad, stream_ptr())
-            gy1 = _gemm_pk(gqkv, m, mpad, wpk.bwd(in_w))
+            gy1 = _gemm_pk(gqkv, m, mpad, _pk(blk, "in", in_w, half, True))
             g, gp = _ln_bwd_part(gy1, xr, ln1_w, mean1, rstd1, g_mid, mpad=mpad)           # through ln_1, + the residual branch
         return g.reshape(b, l, dim), None, None, None
 
@@ -425,9 +416,7 @@ def vision_forward(vit, image):
     x = layer_norm(x, vit.ln_pre)
     if _v2_ok(vit, width):
         half = getattr(vit, "_w2e_precision", "f32") == "f16"
-        if not hasattr(vit, "_wpk") or vit._wpk.half != half:
-            vit._wpk = _WeightsPk(half)
-        x = _TransformerV3.apply(x, vit.heads, vit._wpk, list(vit.transformer.resblocks))
+        x = _TransformerV3.apply(x, vit.heads, half, list(vit.transformer.resblocks))
     else:  # widths the M = 50*batch kernels are not instantiated for (the tests' tiny tower): first-generation kernels
         arena = None if os.environ.get("W2E_TUNE_NO_ARENA") else _ZeroArena(len(vit.transformer.resblocks), x.device)
         for blk in vit.transformer.resblocks:
@@ -461,7 +450,7 @@ def text_hip_ok(clip, tokens):
 def text_forward(clip, tokens):
     """CLIP.encode_text on the block kernels: embed -> per block the visual tower's forward (_block_fwd) with the causal attention
     kernel in place of attn2 -> EOT pooling + ln_final -> text_projection.  Forward only (no autograd node: the input is integer tokens
-    and the tower is frozen); the packed weights are cached per parameter version in clip._text_wpk."""
+    and the tower is frozen)."""
     b, l = tokens.shape
     dim = clip.transformer.width
     heads = clip.transformer.resblocks[0].attn.n_head
@@ -471,9 +460,6 @@ def text_forward(clip, tokens):
     emb = clip.token_embedding.weight
     if b == 0:
         return torch.empty((0, clip.text_projection.shape[1]), device=dev, dtype=torch.float32)
-    if not hasattr(clip, "_text_wpk"):
-        clip._text_wpk = _WeightsPk(False)
-    wpk = clip._text_wpk
     m = b * l
     with torch.no_grad():
         x = torch.empty((m, dim), device=dev, dtype=torch.float32)
@@ -481,7 +467,7 @@ def text_forward(clip, tokens):
              ptr(_c(clip.positional_embedding.detach())), ptr(x), b, l, dim, stream_ptr())
         pend, pbias, pres = x.view(1, m, dim), None, None
         for blk in clip.transformer.resblocks:
-            (pend, pbias, pres), _ = _block_fwd(blk, _block_params(blk), pend, pbias, pres, (b, l, dim, heads), wpk, "w2e_attn_causal_fwd")
+            (pend, pbias, pres), _ = _block_fwd(blk, _block_params(blk), pend, pbias, pres, (b, l, dim, heads), False, "w2e_attn_causal_fwd")
         pooled = torch.empty((b, dim), device=dev, dtype=torch.float32)
         call("w2e_text_pool", ptr(pend), pend.shape[0], m * dim, ptr(pbias), ptr(pres), ctypes.c_void_p(tok.data_ptr()), tbytes, b, l,
              ptr(clip.ln_final.weight.detach()), ptr(clip.ln_final.bias.detach()), float(clip.ln_final.eps), ptr(pooled), dim, stream_ptr())
