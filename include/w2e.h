@@ -48,7 +48,9 @@ extern "C" {
  * transposed copy); w2e_mapper_gather and w2e_mapper_transpose are gone; w2e_ranger_step (K13, the optimizer update as one launch) is
  * new.  The library and its one caller (where2edit_amd/) are built from the same tree, and the host tests pin the number.
  * Still 7, additive: w2e_adam_step (K13b) and w2e_rstyle_* (K12e, w2e_attention.h: the region-attention net's style branch); and
- * w2e_conv3x3_plan (the conv dispatcher's decision as a host-side query). */
+ * w2e_conv3x3_plan (the conv dispatcher's decision as a host-side query).
+ * Still 7, although not additive: w2e_wino_plan (which form a stride-1 3x3 conv takes, and the GEMM form's tiles / K split / workspace)
+ * supersedes w2e_wino_gemm_plan, which is gone.  As above: one caller, built from the same tree. */
 #define W2E_VERSION 7
 
 int w2e_version(void);
@@ -217,9 +219,7 @@ int w2e_wino_fused(const float* x, const float* in_scale, const float* uf, const
  * (model.py:270-274; models/facial_recognition/helpers.py:97-119) -- the wide same-resolution layers (N % 64 == 0, K % 8 == 0;
  * H, W multiples of 4 -- or not, with the plain and the bias + PReLU epilogues only: tiles then = ceil(H/4) * ceil(W/4) and the
  * outputs of the last tile row / column past the image are not stored: IR-SE50's 14^2 / 7^2 stages).  Replaces the host-side composition w2e_wino_input -> vendor strided-batched GEMM -> w2e_wino_output:
- *   w2e_wino_gemm_plan   for one layer call: tiles_padded (T = batch*ceil(H/4)*ceil(W/4) rounded up to 32), the K split the library would use
- *                        (1 = none; small layers split K so that 256 CUs have work) and the floats of `workspace` w2e_wino_gemm needs
- *                        (fused-dot partials + split-K slabs; may be 0).  vf must hold 36 * K * tiles_padded floats.
+ *   (w2e_wino_plan, below: tiles_padded, the K split and the floats of `workspace` for one layer call.  vf must hold 36 * K * tiles_padded floats.)
  *   w2e_wino_pack_input  x [B,K,H,W], in_scale [B,K] or NULL -> vf [36][K/8][2][tiles_padded][4]: B^T (in_scale * window) B in the
  *                        order the MFMA consumes it: (xi, kc, h, t, c) = V[xi][k = 8*kc + 2*c + h][t], t = (b, tile row, tile column)
  *   w2e_wino_gemm        y = epilogue(out_scale * A^T [sum_k U V] A) from uf (w2e_wino_weights_fused) and vf.  One workgroup = 64
@@ -231,11 +231,36 @@ int w2e_wino_fused(const float* x, const float* in_scale, const float* uf, const
  *                        its raw A^T M A into a slab of `workspace`, a second launch sums the slabs in order and applies the epilogue.
  *                        No fp32 atomics on any path: results are bit-reproducible ("deterministic" hosts may use it).
  * Rounding as the other F(4x4,3x3) forms: ~1e-5 max-norm relative to a float64 convolution at K = 128 ... 512. */
-int w2e_wino_gemm_plan(int batch, int k_ch, int n_ch, int h, int w, int* tiles_padded, int* splits, int64_t* workspace_floats);
 int w2e_wino_pack_input(const float* x, const float* in_scale, float* vf, int batch, int k_ch, int h, int w, int tiles_padded, void* stream);
 int w2e_wino_gemm(const float* uf, const float* vf, const float* out_scale, float* y, int batch, int k_ch, int n_ch, int h, int w,
                   int tiles_padded, int splits, float* workspace, int act, const float* noise, const float* noise_w, const float* bias,
                   const float* slope, const float* dot_with, float* dot_out, void* stream);
+
+/* Which form one stride-1 (W2E_CONV_SAME) 3x3 conv takes -- the direct kernel, K1g or K1w -- after the library's current options (host
+ * code, no GPU: it looks at the arguments and the options, never at a tensor).  The shape rules it answers from are the ones
+ * w2e_wino_fused / w2e_wino_pack_input / w2e_wino_gemm refuse a call by.
+ *   family         whose policy: the generator's StyledConvs (fixed thresholds; never the ragged GEMM form), or the encoders' and critics'
+ *                  plain convs (IR-SE50, e4e, VGG, the discriminator: by the work per call; ragged tiles allowed)
+ *   request        W2E_WINO_AUTO = the family's measured choice; 0 = the direct kernel; 4 / 8 = that form wherever it fits, else direct
+ *   fused_allowed  0: never form 8 (A/B aid)
+ *   epilogue       W2E_WINO_EPI_*: what the launch will be asked for (the ragged GEMM form has no StyledConv activation and no fused dot;
+ *                  the fused dot needs a tile count it can segment)
+ *   force_splits   > 0: that K split for form 4 instead of the library's (tests); 0 = none
+ * "conv_precision" = bf16x3 and a tile forced by "tune_cfg" mean the direct kernel, whatever the request.
+ * out[W2E_WINO_PLAN_FIELDS] = form (0, 4 or 8), fits_gemm, fits_fused (whether the family could run that form on the shape at all --
+ * both 0 for an empty batch), and for a shape the GEMM form fits, else 0: tiles_padded (batch * ceil(H/4) * ceil(W/4) rounded up to 32),
+ * splits (1 = none; small layers split K so that 256 CUs have work), workspace_floats (fused-dot partials + split-K slabs) -- the
+ * arguments of w2e_wino_pack_input / w2e_wino_gemm. */
+#define W2E_WINO_GENERATOR 0
+#define W2E_WINO_ENCODER 1
+#define W2E_WINO_AUTO (-1)
+#define W2E_WINO_EPI_PLAIN 0 /* the first three are the launchers' `act` */
+#define W2E_WINO_EPI_ACT 1   /* StyledConv: noise_w*noise + bias, LeakyReLU 0.2, sqrt 2 */
+#define W2E_WINO_EPI_PRELU 2 /* + bias, PReLU(slope) */
+#define W2E_WINO_EPI_DOT 3   /* dot_with / dot_out */
+#define W2E_WINO_PLAN_FIELDS 6
+int w2e_wino_plan(int family, int request, int fused_allowed, int epilogue, int batch, int k_ch, int n_ch, int h, int w, int force_splits,
+                  int64_t* out);
 
 /* Demodulation coefficients and their style gradient (model.py:241-243), [B,C]-sized:
  *   d[b,o] = rsqrt(sum_i s[b,i]^2 * wsq[o,i] + eps),  wsq[o,i] = sum_k (scale*W[o,i,k])^2  [cout,cin]. */

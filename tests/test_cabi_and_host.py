@@ -103,9 +103,12 @@ def test_a_caller_with_another_planar_pitch_is_refused_not_read_past(lib):
 def test_winograd_selection_is_host_logic_and_respects_the_4gb_descriptor(lib, monkeypatch):
     """the fused kernel addresses x through ONE buffer descriptor (< 4 GB).  At total batch 32 the 32 @ 1024^2
     layer is exactly 4 GiB: the selection must fall back (here: to the direct kernel) instead of handing w2e_wino_fused a tensor it
-    refuses; likewise 64 @ 512^2 at 64 and 128 @ 256^2 at 128 (there the GEMM form takes over).  No GPU: shapes only."""
+    refuses; likewise 64 @ 512^2 at 64 and 128 @ 256^2 at 128 (there the GEMM form takes over).  No GPU: shapes only, decided by the
+    library (w2e_wino_plan) under its real options."""
     from where2edit_amd import _lib, functional as K
-    monkeypatch.setattr(_lib, "get_option", lambda name: {"conv_precision": 0, "deterministic": 0, "tune_cfg": -1}[name])
+    for name, value in (("conv_precision", "f32"), ("deterministic", "0"), ("tune_cfg", "")):
+        _lib.set_option(name, value)
+    assert (_lib.get_option("conv_precision"), _lib.get_option("deterministic"), _lib.get_option("tune_cfg")) == (0, 0, -1)
     monkeypatch.setattr(K, "WINOGRAD", "auto")
 
     class X:  # _wino_form only reads the batch
@@ -119,16 +122,15 @@ def test_winograd_selection_is_host_logic_and_respects_the_4gb_descriptor(lib, m
     assert K._wino_form(X(128), 128, 128, 256, 256, None) == 0          # (the GEMM form's V would be 9.7 GB here: past ITS descriptor too)
     assert K._wino_form(X(8), 512, 512, 64, 64, None) == 4 and K._wino_form(X(8), 256, 256, 128, 128, X(8)) == 4
     assert K._wino_form(X(8), 512, 512, 8, 8, None) == 0 and K._wino_form(X(8), 512, 256, 64, 64, None) == 4
-    assert not K._gemm_shape_ok(8, 512, 48, 64, 64) and not K._gemm_shape_ok(8, 20, 64, 64, 64) and not K._gemm_shape_ok(8, 64, 64, 30, 32)
-    assert K._gemm_shape_ok(16, 128, 256, 28, 28, dot=False) and not K._gemm_shape_ok(16, 128, 256, 28, 28, dot=True)  # 49 tiles: no fused dot
-    # the plan entry point is host code too: padded tiles, K split for the layers that would leave CUs idle, workspace size
-    tp, sp, ws = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
-    lib.w2e_wino_gemm_plan.argtypes = None
-    assert lib.w2e_wino_gemm_plan(8, 512, 512, 64, 64, ctypes.byref(tp), ctypes.byref(sp), ctypes.byref(ws)) == 0
-    assert (tp.value, sp.value, ws.value) == (2048, 1, 8 * 512 * 8)
-    assert lib.w2e_wino_gemm_plan(3, 64, 64, 28, 28, ctypes.byref(tp), ctypes.byref(sp), ctypes.byref(ws)) == 0
-    assert tp.value == 160 and sp.value >= 1 and ws.value == 3 * 64 * 1 + (sp.value * 3 * 64 * 28 * 28 if sp.value > 1 else 0)
-    assert lib.w2e_wino_gemm_plan(8, 512, 48, 64, 64, ctypes.byref(tp), ctypes.byref(sp), ctypes.byref(ws)) != 0  # N % 64
+    gemm_fits = lambda b, k, n, h, w, epilogue=K.EPI_DOT, family=K.GENERATOR: bool(K.wino_plan(family, b, k, n, h, w, epilogue)[1])
+    assert not gemm_fits(8, 512, 48, 64, 64) and not gemm_fits(8, 20, 64, 64, 64) and not gemm_fits(8, 64, 64, 30, 32)
+    assert gemm_fits(16, 128, 256, 28, 28, K.EPI_PLAIN) and not gemm_fits(16, 128, 256, 28, 28, K.EPI_DOT)  # 49 tiles: no fused dot
+    # the same query is the GEMM form's plan: padded tiles, K split for the layers that would leave CUs idle, workspace size
+    _, fits, _, tp, sp, ws = K.wino_plan(K.GENERATOR, 8, 512, 512, 64, 64)
+    assert fits and (tp, sp, ws) == (2048, 1, 8 * 512 * 8)
+    _, fits, _, tp, sp, ws = K.wino_plan(K.GENERATOR, 3, 64, 64, 28, 28)
+    assert fits and tp == 160 and sp >= 1 and ws == 3 * 64 * 1 + (sp * 3 * 64 * 28 * 28 if sp > 1 else 0)
+    assert K.wino_plan(K.GENERATOR, 8, 512, 48, 64, 64)[1:] == [0, 0, 0, 0, 0]  # N % 64, and K = 512 is past the fused kernel
     with pytest.raises(ValueError):
         K._parse_winograd("off")  # (an unknown value used to mean "auto")
     with pytest.raises(ValueError):

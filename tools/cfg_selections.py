@@ -25,7 +25,7 @@ def one_step(workload, batch):
     mask = bench.make_mask(coach, batch, 1024, 0, dev) if workload == 3 else None
     coach.train_step(w, mask)  # builds the lazily cached packs (their launches are not part of a steady-state step)
     lines, wino = conv_selections(lambda: coach.train_step(w, mask))
-    lines += wino  # (the Winograd-form layers are chosen on the Python side: functional._wino_ok)
+    lines += wino  # (the Winograd-form layers: chosen by w2e_wino_plan, their lines written by functional.wino_conv)
     del coach
     torch.cuda.empty_cache()
     return lines

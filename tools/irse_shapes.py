@@ -29,13 +29,14 @@ for B, Ci, C, H in shapes:
     run = lambda form: I.conv3x3(x, wp, C, H, H, bias=bias, slope=slope, form=form)
     base = timeit(lambda: run(0))
     res.append(f"direct {base:6.1f}us ({flop / base / 1e6:5.1f} TF/s)")
-    if K._gemm_shape_ok(B, Ci, C, H, H, dot=False, ragged=True):
+    chosen, gemm_fits, fused_fits, *_ = K.wino_plan(K.ENCODER, B, Ci, C, H, H, K.EPI_PRELU, fused_allowed=I.FUSED_ENCODER)
+    if gemm_fits:
         t = timeit(lambda: run(4))
         res.append(f"F(4x4) gemm {t:6.1f}us ({flop / t / 1e6:5.1f})")
-    if K._fused_shape_ok(B, Ci, C, H, H):
+    if fused_fits:
         t = timeit(lambda: run(K.FUSED))
         res.append(f"fused {t:6.1f}us ({flop / t / 1e6:5.1f})")
-    res.append(f"chosen: {({0: 'direct', K.FUSED: 'fused'}).get(I._wino_form(B, Ci, C, H, H), I._wino_form(B, Ci, C, H, H))}")
+    res.append(f"chosen: {({0: 'direct', K.FUSED: 'fused'}).get(chosen, chosen)}")
     if sweep:
         best = (1e9, None)
         for cfg in range(0, 11):

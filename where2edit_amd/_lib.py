@@ -46,7 +46,7 @@ _PROTOS = {
     "w2e_modconv_down_rgbfold": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _F, _P]),
     "w2e_wino_weights_fused": (_I, [_P, _P, _I, _I, _P]),
     "w2e_wino_fused": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
-    "w2e_wino_gemm_plan": (_I, [_I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64)]),
+    "w2e_wino_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int64)]),
     "w2e_wino_pack_input": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "w2e_wino_gemm": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "w2e_demod_fwd": (_I, [_P, _P, _P, _I, _I, _I, _F, _P]),

@@ -10,6 +10,9 @@
 namespace w2e {
 
 void set_error(const char* fmt, ...);
+// The text of a refusal (thread-local, valid until the thread's next call): for rule functions that return "why not" or nullptr, so
+// that a launcher can refuse with it (W2E_REQUIRE(!why, "%s", why)) and a plan can merely ask.
+const char* refusal(const char* fmt, ...);
 
 // Process-wide options (runtime.hip): read from the environment once at library load, changed by w2e_set_option().
 struct Options {

@@ -19,6 +19,15 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
+const char* refusal(const char* fmt, ...) {
+    static thread_local char text[256];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(text, sizeof(text), fmt, ap);
+    va_end(ap);
+    return text;
+}
+
 static Options g_opt;
 
 static int parse_precision(const char* v) { return (v && strcmp(v, "bf16x3") == 0) ? 1 : 0; }

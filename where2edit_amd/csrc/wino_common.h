@@ -27,4 +27,15 @@ __device__ __forceinline__ void wino4_at(const T (&m)[6], T (&y)[4]) {  // y = A
     y[3] = q + 8.f * s + m[5];
 }
 
+// ---- host side: the shape rules of the two forms, written once.  Each returns why the form cannot take a shape -- the text its launcher
+// refuses the call with, behind `who` -- or nullptr; w2e_wino_plan reads "fits" from the same functions.  Shapes only (epilogue: a
+// W2E_WINO_EPI_* code): pointers, alignment and the consistency of the other arguments stay with the launchers.
+const char* wino_fused_refusal(int batch, int k_ch, int n_ch, int h, int w);                                               // winograd.hip
+const char* wino_pack_refusal(const char* who, int batch, int k_ch, int h, int w, int64_t tiles_padded);                   // winogemm.hip
+const char* wino_gemm_refusal(int epilogue, int batch, int k_ch, int n_ch, int h, int w, int64_t tiles_padded);            // winogemm.hip
+
+constexpr int64_t kWinoDescLimit = ((int64_t)1 << 32) - 64;  // bytes behind ONE buffer descriptor (x of the fused kernel; U, V of the GEMM form)
+// a * b >= limit for a, b >= 0, without forming the product (the rules are asked about any int a caller can pass)
+static inline bool wino_prod_reaches(int64_t a, int64_t b, int64_t limit) { return b != 0 && a > (limit - 1) / b; }
+
 }  // namespace w2e

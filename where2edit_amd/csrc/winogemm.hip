@@ -334,14 +334,38 @@ __global__ __launch_bounds__(256) void wino_dot_sum_kernel(const float* __restri
     dot_out[plane] += s;
 }
 
-static int plan(int batch, int k_ch, int n_ch, int h, int w, int* tp, int* splits, int64_t* ws_floats, int* nseg_out, int force_splits) {
-    const int tiles = ((h + 3) / 4) * ((w + 3) / 4);
-    const int64_t T = (int64_t)batch * tiles;
-    const int64_t TP = (T + 31) & ~(int64_t)31;
+// The GEMM form's shape rules (wino_common.h), in two steps: what w2e_wino_pack_input needs of (K, the image, tiles_padded) -- V behind ONE
+// buffer descriptor --, and what w2e_wino_gemm needs on top: N, U behind a descriptor of its own, and what the epilogue takes.
+const char* wino_pack_refusal(const char* who, int batch, int k_ch, int h, int w, int64_t tiles_padded) {
+    if (batch < 0 || k_ch <= 0 || (k_ch & 7) != 0 || h < 4 || w < 4) return refusal("%s: batch >= 0, K %% 8 == 0 and H, W >= 4 (got %d, K %d, %d x %d)", who, batch, k_ch, h, w);
+    const int64_t tiles = (((int64_t)h + 3) / 4) * (((int64_t)w + 3) / 4);
+    if (wino_prod_reaches(batch, tiles, (int64_t)1 << 30)) return refusal("%s: too many tiles", who);
+    const int64_t T = batch * tiles;
+    if (tiles_padded < T || (tiles_padded & 31) != 0) return refusal("%s: tiles_padded %lld for %lld tiles (w2e_wino_plan)", who, (long long)tiles_padded, (long long)T);
+    if (wino_prod_reaches((int64_t)36 * 4 * k_ch, tiles_padded, kWinoDescLimit)) return refusal("%s: V exceeds 4 GB", who);
+    return nullptr;
+}
+
+const char* wino_gemm_refusal(int epilogue, int batch, int k_ch, int n_ch, int h, int w, int64_t tiles_padded) {
+    if (const char* why = wino_pack_refusal("wino_gemm", batch, k_ch, h, w, tiles_padded)) return why;
+    if (n_ch <= 0 || (n_ch & 63) != 0) return refusal("wino_gemm: N %% 64 == 0 (got %d)", n_ch);
+    if (wino_prod_reaches((int64_t)36 * 4 * k_ch, n_ch, kWinoDescLimit)) return refusal("wino_gemm: U exceeds 4 GB");
+    const bool dot = epilogue == W2E_WINO_EPI_DOT;
+    // tiles = ceil(H/4) x ceil(W/4); the ragged form stores no outputs past the image, and has neither noise nor a fused dot
+    if (((h | w) & 3) != 0 && (dot || epilogue == W2E_WINO_EPI_ACT)) return refusal("wino_gemm: H, W that are not multiples of 4 take the plain and the bias + PReLU epilogues only");
+    const int64_t tiles = (((int64_t)h + 3) / 4) * (((int64_t)w + 3) / 4);
+    // the fused dot reduces over the lanes of a half-wave that share an image: whole 32-tile segments, or a power of two below
+    if (dot && (tiles & 31) != 0 && !(tiles < 32 && (tiles & (tiles - 1)) == 0))
+        return refusal("wino_gemm: fused dot with %lld tiles per plane (a multiple of 32, or a power of two below it)", (long long)tiles);
+    return nullptr;
+}
+
+// The K split of one w2e_wino_gemm call (force_splits > 0: that many, tests) -> chunks per split; *splits = the splits that are not empty.
+static int gemm_splits(int batch, int k_ch, int n_ch, int h, int w, int64_t TP, int force_splits, int* splits) {
     const int KC = k_ch / 8;
     const int64_t G = (int64_t)(n_ch / 64) * (TP / 32);
     int S = 1;
-    if (force_splits > 0) S = force_splits;
+    if (force_splits > 0) S = force_splits < KC ? force_splits : KC;
     else if (G < 192 && (int64_t)h * w <= 64 * 64) {  // too few workgroups for 256 CUs: split K (slabs of <= 64^2 planes, summed per wave)
         const int cus = cu_count();
         S = (int)((cus + G - 1) / G);
@@ -349,11 +373,8 @@ static int plan(int batch, int k_ch, int n_ch, int h, int w, int* tp, int* split
         if (S > 16) S = 16;
         if (S < 1) S = 1;
     }
-    int kcs = (KC + S - 1) / S;
-    S = (KC + kcs - 1) / kcs;
-    const int nseg = tiles >= 32 ? tiles / 32 : 1;
-    *tp = (int)TP, *splits = S, *nseg_out = nseg;
-    *ws_floats = (int64_t)batch * n_ch * nseg + (S > 1 ? (int64_t)S * batch * n_ch * h * w : 0);
+    const int kcs = (KC + S - 1) / S;
+    *splits = (KC + kcs - 1) / kcs;
     return kcs;
 }
 
@@ -363,25 +384,65 @@ using namespace w2e;
 
 extern "C" {
 
-int w2e_wino_gemm_plan(int batch, int k_ch, int n_ch, int h, int w, int* tiles_padded, int* splits, int64_t* workspace_floats) {
-    W2E_REQUIRE(tiles_padded && splits && workspace_floats, "wino_gemm_plan: null output");
-    W2E_REQUIRE(batch >= 0 && k_ch > 0 && (k_ch & 7) == 0 && n_ch > 0 && (n_ch & 63) == 0, "wino_gemm_plan: K %% 8 == 0, N %% 64 == 0 (got %d, %d)", k_ch, n_ch);
-    W2E_REQUIRE(h >= 4 && w >= 4, "wino_gemm_plan: H, W >= 4 (got %d x %d)", h, w);
-    W2E_REQUIRE((int64_t)batch * ((h + 3) / 4) * ((w + 3) / 4) < ((int64_t)1 << 30), "wino_gemm_plan: too many tiles");
-    int nseg = 0;
-    plan(batch, k_ch, n_ch, h, w, tiles_padded, splits, workspace_floats, &nseg, 0);
+// Which form a same-resolution 3x3 conv takes (include/w2e.h).  The two families' policies, each as measured:
+//   generator  auto = form 4 for K, N >= 128 at 16^2 ... 256^2 (K = N = 256 / 512), the fused kernel for 128 @ 256^2, 64 @ 512^2,
+//              32 @ 1024^2, the direct kernels for the rest (<= 8^2); never the ragged GEMM form.
+//   encoder    (IR-SE50 / e4e / VGG / the discriminator; profiles/r05_irse_shapes.txt, the fused kernel with 64 output channels per
+//              workgroup where the grid fills the chip; batch 8 of the e4e encoder / batch 16 of the id-loss network, us, direct / GEMM
+//              form / fused): 64 -> 64 @ 256^2 306 / 255 / 137; 64 -> 64 @ 128^2 81 / 49 / 37; 64 -> 128 @ 128^2 148 / 73 / 73;
+//              128 -> 128 @ 64^2 81 / 51 / 41 (32-channel workgroups: 64 blocks); 128 -> 256 @ 64^2 152 / 58 / 59; 256 -> 256 @ 32^2
+//              88 / 44 / 103; 64 -> 64 @ 112^2 (batch 16) 163 / 89 / -; 64 -> 128 @ 56^2 87 / 42; 128 -> 256 @ 28^2 80 / 55;
+//              256 -> 256 @ 14^2 54 / 45; 256 -> 512 @ 14^2 89 / 53; 512 -> 512 @ 7^2 65 / 50 (14^2 / 7^2: the ragged form); below
+//              ~3 GFLOP of direct work per call the direct kernel wins, it pays for no second or third launch (64 -> 64 @ 56^2, batch 8:
+//              26 / 39; 256 -> 256 @ 14^2, batch 8: 33 / 42).  The fused kernel repeats its input transform per 32 output channels, the
+//              GEMM form pays one pass over V: fused where the layer does not widen (N <= K <= 128), the GEMM form otherwise.
+// bf16x3 and a tile forced by tune_cfg (tests, tools/layer_bench.py) mean the direct kernel.  Bit-reproducible mode keeps both forms:
+// the fused kernel leaves per-block partials of its fused dot, the GEMM form per-segment partials and K-split slabs -- all summed in a
+// fixed order, no atomics.
+int w2e_wino_plan(int family, int request, int fused_allowed, int epilogue, int batch, int k_ch, int n_ch, int h, int w, int force_splits,
+                  int64_t* out) {
+    W2E_REQUIRE(out != nullptr, "wino_plan: null argument");
+    W2E_REQUIRE(family == W2E_WINO_GENERATOR || family == W2E_WINO_ENCODER, "wino_plan: family %d (0 generator, 1 encoder)", family);
+    W2E_REQUIRE(request == W2E_WINO_AUTO || request == 0 || request == 4 || request == 8, "wino_plan: request %d (-1 auto, 0 direct, 4, 8)", request);
+    W2E_REQUIRE(epilogue >= W2E_WINO_EPI_PLAIN && epilogue <= W2E_WINO_EPI_DOT, "wino_plan: epilogue %d (0 plain, 1 StyledConv, 2 bias + PReLU, 3 fused dot)", epilogue);
+    W2E_REQUIRE(batch >= 0 && force_splits >= 0, "wino_plan: batch %d, forced splits %d", batch, force_splits);
+    const bool ragged = ((h | w) & 3) != 0;
+    const int64_t tiles = (((int64_t)h + 3) / 4) * (((int64_t)w + 3) / 4);
+    const int64_t TP = (h < 4 || w < 4 || wino_prod_reaches(batch, tiles, (int64_t)1 << 30)) ? 0 : (batch * tiles + 31) & ~(int64_t)31;
+    const bool fit4 = batch > 0 && !(family == W2E_WINO_GENERATOR && ragged) && !wino_gemm_refusal(epilogue, batch, k_ch, n_ch, h, w, TP);
+    const bool fit8 = batch > 0 && !wino_fused_refusal(batch, k_ch, n_ch, h, w);
+    const bool use8 = fit8 && fused_allowed != 0;
+    int m = 0;
+    if (options().conv_precision != 0 || options().tune_cfg >= 0) m = 0;
+    else if (request == 4) m = fit4 ? 4 : 0;
+    else if (request == 8) m = use8 ? 8 : 0;
+    else if (request == W2E_WINO_AUTO && family == W2E_WINO_GENERATOR) {
+        if (k_ch <= 128 && n_ch <= 128 && h >= 256 && w >= 256 && use8) m = 8;
+        else if (k_ch >= 128 && n_ch >= 128 && h >= 16 && h <= 256 && w >= 16 && w <= 256 && fit4) m = 4;
+    } else if (request == W2E_WINO_AUTO && 18.0 * batch * k_ch * n_ch * h * w >= 3e9) {
+        if (use8 && k_ch <= 128 && n_ch <= k_ch) m = 8;
+        else if (fit4 && k_ch >= 64) m = 4;
+        else if (use8 && k_ch <= 128) m = 8;
+    }
+    int splits = 0;
+    int64_t ws = 0;
+    if (fit4) {  // (whatever `m` is: a caller that forces form 4 against the policy launches with these)
+        gemm_splits(batch, k_ch, n_ch, h, w, TP, force_splits, &splits);
+        const int64_t nseg = tiles >= 32 ? tiles / 32 : 1;  // fused-dot partials [B,N,nseg], then the K-split slabs [S][B,N,H,W]
+        ws = (int64_t)batch * n_ch * nseg + (splits > 1 ? (int64_t)splits * batch * n_ch * h * w : 0);
+    }
+    out[0] = m, out[1] = fit4, out[2] = fit8, out[3] = fit4 ? TP : 0, out[4] = splits, out[5] = ws;
     return 0;
 }
 
 int w2e_wino_pack_input(const float* x, const float* in_scale, float* vf, int batch, int k_ch, int h, int w, int tiles_padded, void* stream) {
     W2E_REQUIRE(x && vf, "wino_pack_input: null tensor");
-    W2E_REQUIRE(batch >= 0 && k_ch > 0 && (k_ch & 7) == 0 && h >= 4 && w >= 4, "wino_pack_input: K %% 8 == 0 and H, W >= 4 (got K %d, %d x %d)", k_ch, h, w);
+    const char* const why = wino_pack_refusal("wino_pack_input", batch, k_ch, h, w, tiles_padded);
+    W2E_REQUIRE(!why, "%s", why);
     const bool ragged = (h & 3) != 0 || (w & 3) != 0;
     W2E_REQUIRE((((uintptr_t)x | (uintptr_t)vf) & 15) == 0, "wino_pack_input: x / vf must be 16-byte aligned");
-    const int64_t T = (int64_t)batch * ((h + 3) / 4) * ((w + 3) / 4);
-    W2E_REQUIRE(tiles_padded >= T && (tiles_padded & 31) == 0, "wino_pack_input: tiles_padded %d for %lld tiles (w2e_wino_gemm_plan)", tiles_padded, (long long)T);
-    W2E_REQUIRE((int64_t)36 * k_ch * tiles_padded * 4 < ((int64_t)1 << 32) - 64, "wino_pack_input: V exceeds 4 GB");
     if (batch == 0) return 0;
+    const int64_t T = (int64_t)batch * ((h + 3) / 4) * ((w + 3) / 4);
     dim3 grid((unsigned)ceil_div(T, 128), (unsigned)(k_ch / 8 * 2));
     if (ragged) wino4_pack_input_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(x, in_scale, vf, batch, k_ch, h, w, tiles_padded);
     else wino4_pack_input_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(x, in_scale, vf, batch, k_ch, h, w, tiles_padded);
@@ -394,10 +455,9 @@ int w2e_wino_gemm(const float* uf, const float* vf, const float* out_scale, floa
                   const float* slope, const float* dot_with, float* dot_out, void* stream) {
     W2E_REQUIRE(uf && vf && y, "wino_gemm: null tensor");
     W2E_REQUIRE(act >= 0 && act <= 2, "wino_gemm: epilogue %d (0 none, 1 StyledConv, 2 bias + PReLU)", act);
-    W2E_REQUIRE(batch >= 0 && k_ch > 0 && (k_ch & 7) == 0 && n_ch > 0 && (n_ch & 63) == 0, "wino_gemm: K %% 8 == 0, N %% 64 == 0 (got %d, %d)", k_ch, n_ch);
-    W2E_REQUIRE(h >= 4 && w >= 4, "wino_gemm: H, W >= 4 (got %d x %d)", h, w);
-    const bool ragged = (h & 3) != 0 || (w & 3) != 0;  // tiles = ceil(H/4) x ceil(W/4); outputs past the image are not stored
-    W2E_REQUIRE(!ragged || (!dot_with && act != 1), "wino_gemm: H, W that are not multiples of 4 take the plain and the bias + PReLU epilogues only");
+    const char* const why = wino_gemm_refusal(dot_with ? W2E_WINO_EPI_DOT : act, batch, k_ch, n_ch, h, w, tiles_padded);
+    W2E_REQUIRE(!why, "%s", why);
+    const bool ragged = (h & 3) != 0 || (w & 3) != 0;
     W2E_REQUIRE(!(act && dot_with), "wino_gemm: the activation epilogues and the fused dot exclude each other");
     W2E_REQUIRE(!dot_with || dot_out, "wino_gemm: dot_with without dot_out");
     W2E_REQUIRE(!noise || noise_w, "wino_gemm: noise without noise_w");
@@ -408,15 +468,10 @@ int w2e_wino_gemm(const float* uf, const float* vf, const float* out_scale, floa
     if (batch == 0) return 0;
     const int tiles = ((h + 3) / 4) * ((w + 3) / 4);
     const int64_t T = (int64_t)batch * tiles;
-    W2E_REQUIRE(T < ((int64_t)1 << 30), "wino_gemm: too many tiles");
-    W2E_REQUIRE(tiles_padded >= T && (tiles_padded & 31) == 0, "wino_gemm: tiles_padded %d for %lld tiles (w2e_wino_gemm_plan)", tiles_padded, (long long)T);
     const int KC = k_ch / 8;
-    W2E_REQUIRE((int64_t)36 * k_ch * tiles_padded * 4 < ((int64_t)1 << 32) - 64 && (int64_t)36 * k_ch * n_ch * 4 < ((int64_t)1 << 32) - 64, "wino_gemm: U or V exceeds 4 GB");
     W2E_REQUIRE(splits >= 1 && splits <= KC, "wino_gemm: %d splits of %d chunks", splits, KC);
-    // the fused dot reduces over the lanes of a half-wave that share an image: whole 32-tile segments, or a power of two below
-    W2E_REQUIRE(!dot_with || (tiles & 31) == 0 || (tiles < 32 && (tiles & (tiles - 1)) == 0), "wino_gemm: fused dot with %d tiles per plane (a multiple of 32, or a power of two below it)", tiles);
     const int nseg = tiles >= 32 ? tiles / 32 : 1;
-    W2E_REQUIRE(!(dot_with || splits > 1) || workspace, "wino_gemm: the fused dot and a split K need the workspace of w2e_wino_gemm_plan");
+    W2E_REQUIRE(!(dot_with || splits > 1) || workspace, "wino_gemm: the fused dot and a split K need the workspace of w2e_wino_plan");
     W2E_REQUIRE(splits == 1 || (int64_t)h * w % 4 == 0 || (!dot_with && act != 1), "wino_gemm: split planes that are not whole float4s take the plain and the bias + PReLU epilogues only");
     hipStream_t s = (hipStream_t)stream;
     WinoGemmArgs a;
@@ -425,7 +480,7 @@ int w2e_wino_gemm(const float* uf, const float* vf, const float* out_scale, floa
     a.ncb = n_ch / 64, a.ntb = tiles_padded / 32;
     a.kcs = (KC + splits - 1) / splits, a.splits = splits;
     a.skip = options().tune_skip;
-    W2E_REQUIRE((int64_t)(splits - 1) * a.kcs < KC, "wino_gemm: %d splits of %d chunks leave an empty split (w2e_wino_gemm_plan)", splits, KC);
+    W2E_REQUIRE((int64_t)(splits - 1) * a.kcs < KC, "wino_gemm: %d splits of %d chunks leave an empty split (w2e_wino_plan)", splits, KC);
     a.nseg = nseg, a.seg = tiles < 32 ? tiles : 32;
     float* const dot_part = workspace;                                            // [B*N*nseg]
     float* const slabs = workspace ? workspace + (int64_t)batch * n_ch * nseg : nullptr;  // [S][B,N,H,W]

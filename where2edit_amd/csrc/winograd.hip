@@ -435,6 +435,18 @@ __global__ __launch_bounds__(64 * (MW + 4), 1) void wino4_fused3_kernel(const fl
     else matrix_role(std::integral_constant<int, 0>{});
 }
 
+// w2e_wino_fused's shape rules (wino_common.h).  The kernel's waves are persistent and specialised -- K a power of two in 32 ... 256 --
+// and range-check their loads against ONE descriptor over x: x < 4 GB (total batch 32 of the 32 @ 1024^2 layer is 4 GiB: the merged
+// [w; w_hat] pass reaches that at batch_size 16; past it the selection falls back to the GEMM form or the direct kernel).
+const char* wino_fused_refusal(int batch, int k_ch, int n_ch, int h, int w) {
+    if (batch < 0 || n_ch <= 0 || (n_ch & 31) != 0) return refusal("wino_fused: batch >= 0, N %% 32 == 0 (got %d, %d)", batch, n_ch);
+    if (k_ch < 32 || k_ch > 256 || (k_ch & (k_ch - 1)) != 0) return refusal("wino_fused: K must be a power of two in 32 ... 256 (got %d)", k_ch);
+    if (h < 16 || w < 32 || (h & 15) != 0 || (w & 31) != 0) return refusal("wino_fused: H %% 16 == 0 and W %% 32 == 0 (got %d x %d)", h, w);
+    if (wino_prod_reaches(batch, (int64_t)(h >> 4) * (w >> 5), (int64_t)1 << 31)) return refusal("wino_fused: too many tile blocks");
+    if (wino_prod_reaches((int64_t)4 * batch * k_ch, (int64_t)h * w, kWinoDescLimit)) return refusal("wino_fused: x exceeds 4 GB");
+    return nullptr;
+}
+
 }  // namespace w2e
 
 using namespace w2e;
@@ -455,8 +467,8 @@ int w2e_wino_fused(const float* x, const float* in_scale, const float* uf, const
                    const float* dot_with, float* dot_out, int wgs, void* stream) {
     W2E_REQUIRE(x && uf && y, "wino_fused: null tensor");
     W2E_REQUIRE(act >= 0 && act <= 2, "wino_fused: epilogue %d (0 none, 1 StyledConv, 2 bias + PReLU)", act);
-    W2E_REQUIRE(batch >= 0 && k_ch > 0 && (k_ch & 7) == 0 && n_ch > 0 && (n_ch & 31) == 0, "wino_fused: K %% 8 == 0, N %% 32 == 0 (got %d, %d)", k_ch, n_ch);
-    W2E_REQUIRE(h >= 16 && w >= 32 && (h & 15) == 0 && (w & 31) == 0, "wino_fused: H %% 16 == 0 and W %% 32 == 0 (got %d x %d)", h, w);
+    const char* const why = wino_fused_refusal(batch, k_ch, n_ch, h, w);
+    W2E_REQUIRE(!why, "%s", why);
     W2E_REQUIRE(!(act && dot_with), "wino_fused: the activation epilogues and the fused dot exclude each other");
     W2E_REQUIRE(!dot_with || dot_out, "wino_fused: dot_with without dot_out");
     W2E_REQUIRE(!noise || noise_w, "wino_fused: noise without noise_w");
@@ -466,11 +478,7 @@ int w2e_wino_fused(const float* x, const float* in_scale, const float* uf, const
                 "wino_fused: x / y / uf / dot_with / noise must be 16-byte aligned");
     if (batch == 0) return 0;
     const int64_t blocks = (int64_t)batch * (h >> 4) * (w >> 5);
-    W2E_REQUIRE(blocks < ((int64_t)1 << 31), "wino_fused: too many tile blocks");
     hipStream_t s = (hipStream_t)stream;
-    // persistent, specialised waves: K a power of two in 32 ... 256; the whole input behind ONE buffer descriptor
-    W2E_REQUIRE(k_ch >= 32 && k_ch <= 256 && (k_ch & (k_ch - 1)) == 0, "wino_fused: K must be a power of two in 32 ... 256 (got %d)", k_ch);
-    W2E_REQUIRE((int64_t)batch * k_ch * h * w * 4 < ((int64_t)1 << 32) - 64, "wino_fused: x exceeds 4 GB");
     int kc_log2 = 0;
     while ((8 << kc_log2) < k_ch) ++kc_log2;
     const int cus = cu_count();

@@ -5,6 +5,7 @@ the stream (kernels are enqueued on torch's current HIP stream) and the autograd
 on image-sized tensors happens in the HIP kernels; torch ops are used only on [B,C]-sized style math.
 """
 import ctypes
+import functools
 import math
 import os
 
@@ -250,8 +251,8 @@ MODE_SAME, MODE_UP, MODE_DOWN = 0, 1, 2
 #               MFMA, operands L2 -> registers, the output transform and the direct kernel's epilogues in its epilogue: M never reaches HBM)
 #   form FUSED  w2e_wino_fused for the narrow high-resolution layers (nothing transform-domain in HBM at all)
 # WINOGRAD (W2E_WINOGRAD, read once here):
-#   "auto"  per layer, what measures fastest: form 4 for K, N >= 128 at 16^2 ... 128^2 (K = N = 256 / 512), FUSED for 128 @ 256^2, 64 @ 512^2,
-#           32 @ 1024^2, the direct kernels for the rest (up-sampling layers, <= 8^2).  Rounding ~1e-5 relative (direct: 3e-7)
+#   "auto"  per layer, what measured fastest: the library's choice (w2e_wino_plan in csrc/winogemm.hip holds the thresholds and the
+#           shape rules of both forms; up-sampling layers always run the direct kernels).  Rounding ~1e-5 relative (direct: 3e-7)
 #   False   direct kernels only ("0");  4 / 8: that form wherever the shapes allow (tests, tools)
 def _parse_winograd(v):
     table = {"": "auto", "auto": "auto", "0": False, "4": 4, "8": 8}
@@ -275,55 +276,29 @@ def set_winograd(mode):
     WINOGRAD = mode
 
 
-FUSED_WGS = 0           # > 0: cap of the fused kernel's persistent grid (tests)
-X_LIMIT = 2 ** 32 - 64  # bytes: the fused kernel addresses the whole input through ONE buffer descriptor
+FUSED_WGS = 0    # > 0: cap of the fused kernel's persistent grid (tests)
+GEMM_SPLITS = 0  # > 0: force w2e_wino_gemm's K split (tests); 0: the library's plan
+
+GENERATOR, ENCODER = 0, 1                         # W2E_WINO_GENERATOR / W2E_WINO_ENCODER: whose selection policy
+EPI_PLAIN, EPI_ACT, EPI_PRELU, EPI_DOT = range(4)  # W2E_WINO_EPI_*: the first three are the launchers' `act`
 
 
-def _fused_shape_ok(b, k, n, h, w, dot=False):
-    """w2e_wino_fused's shape rules (include/w2e.h, K1w).  It range-checks its loads against one descriptor over x, so it needs
-    x < 4 GB (total batch 32 of the 32 @ 1024^2 layer is 4 GiB: the merged [w; w_hat] pass reaches that at batch_size 16) -- past it
-    the selection falls back to the GEMM form or the direct kernel, which only needs one image under 4 GB."""
-    if not (b > 0 and n % 32 == 0 and h % 16 == 0 and w % 32 == 0 and b * (h // 16) * (w // 32) < 2 ** 31):
-        return False
-    return 32 <= k <= 256 and k & (k - 1) == 0 and 4 * b * k * h * w < X_LIMIT
+_WinoPlanFields = ctypes.c_int64 * 6  # W2E_WINO_PLAN_FIELDS
 
 
-def _gemm_shape_ok(b, k, n, h, w, dot=True, ragged=False):
-    """w2e_wino_gemm's shape rules (include/w2e.h, K1g).  `ragged`: the caller accepts the form for H, W that are not multiples of 4
-    (tiles hang over the image; plain and bias + PReLU epilogues only: the encoders' 14^2 / 7^2 stages)."""
-    if b <= 0 or k % 8 or n % 64 or h < 4 or w < 4:
-        return False
-    if (h % 4 or w % 4) and (dot or not ragged):
-        return False
-    tiles = -(-h // 4) * -(-w // 4)
-    tp = (b * tiles + 31) & ~31
-    if 36 * k * tp * 4 >= X_LIMIT or 36 * k * n * 4 >= X_LIMIT or b * tiles >= 2 ** 30:
-        return False
-    return (not dot) or tiles % 32 == 0 or (tiles < 32 and tiles & (tiles - 1) == 0)  # (the fused dot reduces over half-wave segments)
+def wino_plan(family, b, k, n, h, w, epilogue=EPI_PLAIN, request=None, fused_allowed=True):
+    """w2e_wino_plan (include/w2e.h): [form, fits_gemm, fits_fused, tiles_padded, splits, workspace_floats] for one W2E_CONV_SAME call --
+    0 (direct kernel), 4 (the GEMM form: w2e_wino_pack_input + w2e_wino_gemm) or FUSED (w2e_wino_fused), whether each form fits the shape
+    at all, and the GEMM form's arguments.  The shape rules and both families' policies live in the library; `request`: None = WINOGRAD."""
+    out = _WinoPlanFields()
+    request = WINOGRAD if request is None else request
+    call("w2e_wino_plan", family, -1 if request == "auto" else int(request), fused_allowed, epilogue, b, k, n, h, w, GEMM_SPLITS, out)
+    return out[:]
 
 
 def _wino_form(x, k, n, h, w, dot_with):
-    """0 (direct kernel), 4 (the GEMM form: w2e_wino_pack_input + w2e_wino_gemm) or FUSED (w2e_wino_fused) for one W2E_CONV_SAME call."""
-    if WINOGRAD is False:
-        return 0
-    b = x.shape[0]
-    dot = dot_with is not None
-    if WINOGRAD == "auto":
-        m = 4 if (k >= 128 and n >= 128 and 16 <= h <= 256 and 16 <= w <= 256) else 0
-        if k <= 128 and n <= 128 and h >= 256 and w >= 256 and _fused_shape_ok(b, k, n, h, w, dot):
-            m = FUSED  # 128 @ 256^2, 64 @ 512^2, 32 @ 1024^2
-    else:
-        m = WINOGRAD
-    if m == FUSED:
-        if not _fused_shape_ok(b, k, n, h, w, dot):
-            return 0
-    elif not m or not _gemm_shape_ok(b, k, n, h, w, dot):
-        return 0
-    if _lib.get_option("conv_precision") != 0:
-        return 0
-    # (bit-reproducible mode keeps both forms: the fused kernel leaves per-block partials of its fused dot, the GEMM form per-segment
-    # partials and K-split slabs -- all summed in a fixed order, no atomics)
-    return m if _lib.get_option("tune_cfg") < 0 else 0  # (a forced direct tile: tests, tools/layer_bench.py)
+    """0, 4 or FUSED for one W2E_CONV_SAME call of the generator."""
+    return wino_plan(GENERATOR, x.shape[0], k, n, h, w, EPI_PLAIN if dot_with is None else EPI_DOT)[0]
 
 
 def _wino_weights_fused(wp, k, n):
@@ -335,56 +310,40 @@ def _wino_weights_fused(wp, k, n):
     return uf
 
 
-GEMM_SPLITS = 0  # > 0: force w2e_wino_gemm's K split (tests); 0: the library's plan
-
-
-def wino_gemm_conv(x, wp, in_scale, out_scale, y, k, n, h, w, act_code=0, noise=None, noise_w=None, bias=None, slope=None,
-                   dot_with=None, dot=None, tag="modconv mode 0"):
-    """One same-resolution 3x3 conv in the F(4x4,3x3) GEMM form (K1g): w2e_wino_pack_input -> w2e_wino_gemm; `dot` [b,n] is accumulated
-    into (in a fixed order, no atomics) when dot_with is given."""
+def wino_conv(m, x, wp, in_scale, out_scale, y, k, n, h, w, act_code=0, noise=None, noise_w=None, bias=None, slope=None,
+              dot_with=None, dot=None, tag="modconv mode 0", plan=None):
+    """One same-resolution 3x3 conv in Winograd form m: FUSED (K1w, w2e_wino_fused) or 4 (K1g, w2e_wino_pack_input -> w2e_wino_gemm with
+    the tiles / K split / workspace of `plan`, a wino_plan() result; None: asked for here).  `dot` [b,n] receives the fused dot when
+    dot_with is given (summed in a fixed order, no atomics).  A shape the form does not take is refused by its launcher."""
     b = x.shape[0]
-    tp, sp, ws = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
-    call("w2e_wino_gemm_plan", b, k, n, h, w, ctypes.byref(tp), ctypes.byref(sp), ctypes.byref(ws))
-    splits = sp.value
-    ws_floats = ws.value
-    if GEMM_SPLITS > 0 and GEMM_SPLITS != splits:
-        splits = min(GEMM_SPLITS, k // 8)
-        kcs = -(-(k // 8) // splits)
-        splits = -(-(k // 8) // kcs)
-        ws_floats = b * n * max(1, -(-h // 4) * -(-w // 4) // 32) + (splits * b * n * h * w if splits > 1 else 0)
-    if WINO_LOG is not None:
-        WINO_LOG.append(f"{tag} (winograd F(4x4,3x3) gemm{', dot' if dot_with is not None else ''}) K {k} N {n} {h}x{w} B {b} -> "
-                        f"36 x [{n}x{k}] x [{k}x{tp.value}], {splits} K split(s)")
-    vf = torch.empty(36 * k * tp.value, device=x.device, dtype=torch.float32)
-    work = torch.empty(ws_floats, device=x.device, dtype=torch.float32) if (splits > 1 or dot_with is not None) else None
-    st = stream_ptr()
-    call("w2e_wino_pack_input", ptr(x), ptr(in_scale), ptr(vf), b, k, h, w, tp.value, st)
-    call("w2e_wino_gemm", ptr(_wino_weights_fused(wp, k, n)), ptr(vf), ptr(out_scale), ptr(y), b, k, n, h, w, tp.value, splits, ptr(work),
-         act_code, ptr(noise), ptr(noise_w), ptr(bias), ptr(slope), ptr(dot_with), ptr(dot), st)
-
-
-def _modconv_wino(m, x, wp, in_scale, out_scale, y, k, n, h, w, act, dot_with, dot):
-    b = x.shape[0]
-    noise = noise_w = bias = None
-    if act is not None:
-        noise, noise_w, bias = act
+    dot_txt = ", dot" if dot_with is not None else ""
     if m == FUSED:
-        if WINO_LOG is not None:
-            WINO_LOG.append(f"modconv mode 0 (winograd F(4x4,3x3) fused{', dot' if dot_with is not None else ''}) "
-                            f"K {k} N {n} {h}x{w} B {b} -> {b * (h // 16) * (w // 32)} blocks of 32 tiles")
-        if dot_with is not None:  # one partial per (spatial block, channel): summed here, in a fixed order
-            nblk = (h // 16) * (w // 32)
-            part = torch.empty((b, n, nblk), device=x.device, dtype=torch.float32)
-            call("w2e_wino_fused", ptr(x), ptr(in_scale), ptr(_wino_weights_fused(wp, k, n)), ptr(out_scale), ptr(y), b, k, n, h, w,
-                 0, None, None, None, None, ptr(dot_with), ptr(part), FUSED_WGS, stream_ptr())
+        nblk = (h // 16) * (w // 32)
+        if WINO_LOG is not None:  # (the encoders' line never carried the block count; recorded selections are compared byte for byte)
+            WINO_LOG.append(f"{tag} (winograd F(4x4,3x3) fused{dot_txt}) K {k} N {n} {h}x{w} B {b}"
+                            + (f" -> {b * nblk} blocks of 32 tiles" if tag == "modconv mode 0" else ""))
+        # the fused dot leaves one partial per (spatial block, channel): summed below, in a fixed order
+        part = torch.empty((b, n, nblk), device=x.device, dtype=torch.float32) if dot_with is not None else None
+        call("w2e_wino_fused", ptr(x), ptr(in_scale), ptr(_wino_weights_fused(wp, k, n)), ptr(out_scale), ptr(y), b, k, n, h, w,
+             act_code, ptr(noise), ptr(noise_w), ptr(bias), ptr(slope), ptr(dot_with), ptr(part), FUSED_WGS, stream_ptr())
+        if part is not None:
             # (a kernel, not aten::sum: that one memsets under capture.)  `dot` arrives zeroed and nothing else adds to it before this
             # call returns -- the partial sums ARE its value: written in place (round 3 summed into a temporary and added that: 2 more launches)
             call("w2e_channel_sums", ptr(part), None, ptr(dot), b, n, nblk, stream_ptr())
-            return
-        call("w2e_wino_fused", ptr(x), ptr(in_scale), ptr(_wino_weights_fused(wp, k, n)), ptr(out_scale), ptr(y), b, k, n, h, w,
-             int(act is not None), ptr(noise), ptr(noise_w), ptr(bias), None, None, None, FUSED_WGS, stream_ptr())
         return
-    wino_gemm_conv(x, wp, in_scale, out_scale, y, k, n, h, w, int(act is not None), noise, noise_w, bias, None, dot_with, dot)
+    _, _, _, tp, splits, ws_floats = plan or wino_plan(ENCODER, b, k, n, h, w, EPI_DOT if dot_with is not None else act_code, 4)
+    if WINO_LOG is not None:
+        WINO_LOG.append(f"{tag} (winograd F(4x4,3x3) gemm{dot_txt}) K {k} N {n} {h}x{w} B {b} -> "
+                        f"36 x [{n}x{k}] x [{k}x{tp}], {splits} K split(s)")
+    vf = torch.empty(36 * k * tp, device=x.device, dtype=torch.float32)
+    work = torch.empty(ws_floats, device=x.device, dtype=torch.float32) if (splits > 1 or dot_with is not None) else None
+    st = stream_ptr()
+    call("w2e_wino_pack_input", ptr(x), ptr(in_scale), ptr(vf), b, k, h, w, tp, st)
+    call("w2e_wino_gemm", ptr(_wino_weights_fused(wp, k, n)), ptr(vf), ptr(out_scale), ptr(y), b, k, n, h, w, tp, splits, ptr(work),
+         act_code, ptr(noise), ptr(noise_w), ptr(bias), ptr(slope), ptr(dot_with), ptr(dot), st)
+
+
+wino_gemm_conv = functools.partial(wino_conv, 4)  # (x, wp, in_scale, out_scale, y, k, n, h, w, ...): the GEMM form alone (tests)
 
 
 def _modconv_raw(mode, x, wp, in_scale, out_scale, h, w, act=None, dot_with=None, out=None, dot_out=None):
@@ -408,10 +367,10 @@ def _modconv_raw(mode, x, wp, in_scale, out_scale, h, w, act=None, dot_with=None
     if act is not None:
         noise, noise_w, bias = act
     # algorithmic FLOPs: 2*K*N*9 per domain pixel (MACs actually needed; SURVEY 2.3 convention)
-    form = _wino_form(x, k, n, h, w, dot_with) if mode == MODE_SAME else 0
-    sp = profiling.span("modconv3x3_wino4" if form else "modconv3x3", 2.0 * b * k * n * 9 * h * w)
-    if form:
-        _modconv_wino(form, x, wp, in_scale, out_scale, y, k, n, h, w, act, dot_with, dot)
+    plan = wino_plan(GENERATOR, b, k, n, h, w, EPI_DOT if dot_with is not None else int(act is not None)) if mode == MODE_SAME else (0,)
+    sp = profiling.span("modconv3x3_wino4" if plan[0] else "modconv3x3", 2.0 * b * k * n * 9 * h * w)
+    if plan[0]:
+        wino_conv(plan[0], x, wp, in_scale, out_scale, y, k, n, h, w, int(act is not None), noise, noise_w, bias, None, dot_with, dot, plan=plan)
     else:
         call("w2e_modconv3x3", mode, ptr(x), ptr(wp), ptr(in_scale), ptr(out_scale), ptr(y), b, k, n, h, w,
              y.shape[-1] if mode == MODE_UP else 0, int(act is not None), ptr(noise), ptr(noise_w), ptr(bias), ptr(dot_with), ptr(dot), stream_ptr())

@@ -10,7 +10,6 @@ import os
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _lib
 from . import functional as K
 from ._lib import call, ptr, stream_ptr
 from .derived import Holder, derived, drop
@@ -49,56 +48,25 @@ FUSED_ENCODER = os.environ.get("W2E_FUSED_ENCODER", "1") != "0"  # (A/B aid: the
 
 
 def _wino_form(b, k, n, h, w):
-    """The Winograd F(4x4,3x3) form (functional.py, K1w / K1g) of one stride-1 3x3 conv of the IR-SE50 / e4e encoders, or 0: the fused kernel
-    for the narrow high-resolution stages, the GEMM form (own MFMA contraction, output transform in its epilogue) where the channel counts
-    allow -- also for 14^2 / 7^2, whose last tile row / column hangs over the image (the ragged form) --, the direct kernel where the call
-    is too small to pay for two or three launches (profiles/r05_irse_shapes.txt)."""
-    if K.WINOGRAD is False:
-        return 0
-    if _lib.get_option("conv_precision") != 0 or _lib.get_option("tune_cfg") >= 0:
-        return 0
-    # Measured per shape (profiles/r05_irse_shapes.txt, the fused kernel with 64 output channels per workgroup where the grid fills the
-    # chip; batch 8 of the e4e encoder / batch 16 of the id-loss network, us, direct / GEMM form / fused): 64 -> 64 @ 256^2 306 / 255 /
-    # 137; 64 -> 64 @ 128^2 81 / 49 / 37; 64 -> 128 @ 128^2 148 / 73 / 73; 128 -> 128 @ 64^2 81 / 51 / 41 (32-channel workgroups: 64
-    # blocks); 128 -> 256 @ 64^2 152 / 58 / 59; 256 -> 256 @ 32^2 88 / 44 / 103; 64 -> 64 @ 112^2 (batch 16) 163 / 89 / -;
-    # 64 -> 128 @ 56^2 87 / 42; 128 -> 256 @ 28^2 80 / 55; 256 -> 256 @ 14^2 54 / 45; 256 -> 512 @ 14^2 89 / 53; 512 -> 512 @ 7^2 65 / 50;
-    # below ~3 GFLOP of direct work per call the direct kernel wins (64 -> 64 @ 56^2, batch 8: 26 / 39; 256 -> 256 @ 14^2, batch 8: 33 / 42).  The fused kernel repeats its input transform per 32 output channels, the GEMM form pays one pass over V:
-    # fused where the layer does not widen (N <= K <= 128), the GEMM form otherwise.
-    work_ok = 18.0 * b * k * n * h * w >= 3e9
-    fused_ok = FUSED_ENCODER and K._fused_shape_ok(b, k, n, h, w)
-    gemm_ok = K._gemm_shape_ok(b, k, n, h, w, dot=False, ragged=True)
-    if K.WINOGRAD == K.FUSED:
-        return K.FUSED if fused_ok else 0
-    if K.WINOGRAD == 4:
-        return 4 if gemm_ok else 0
-    if not work_ok:
-        return 0
-    if fused_ok and k <= 128 and n <= k:
-        return K.FUSED
-    if gemm_ok and k >= 64:
-        return 4
-    return K.FUSED if (fused_ok and k <= 128) else 0
+    """The Winograd F(4x4,3x3) form (functional.py, K1w / K1g) of one stride-1 3x3 conv of the IR-SE50 / e4e encoders, or 0: the encoder
+    family's policy of w2e_wino_plan (csrc/winogemm.hip, with the per-shape timings behind it)."""
+    return K.wino_plan(K.ENCODER, b, k, n, h, w, fused_allowed=FUSED_ENCODER)[0]
 
 
 def conv3x3(x, wp, n_out, h, w, mode=K.MODE_SAME, down_pad=0, in_scale=None, out_scale=None, bias=None, slope=None, out=None, form=None):
     """w2e_conv3x3.  h,w: input size for SAME / UP, output size for DOWN.  in_scale [B,K] / out_scale [B,N] / bias, slope [N].
-    `out`: a contiguous [B,n_out,h,w] tensor to write (SAME / DOWN).  `form`: None = the library's / _wino_form's choice;
-    0 / 4 / 8 force the direct kernel / a Winograd form (tools/irse_shapes.py)."""
+    `out`: a contiguous [B,n_out,h,w] tensor to write (SAME / DOWN).  `form`: None = the library's choice (w2e_wino_plan);
+    0 / 4 / 8 force the direct kernel / a Winograd form, which refuses a shape it does not take (tools/irse_shapes.py)."""
     b, k = x.shape[0], x.shape[1]
-    if mode == K.MODE_SAME and b > 0:
-        m = _wino_form(b, k, n_out, h, w) if form is None else form
+    if mode == K.MODE_SAME and b > 0 and form != 0:
+        epi = K.EPI_PRELU if (bias is not None or slope is not None) else K.EPI_PLAIN
+        plan = K.wino_plan(K.ENCODER, b, k, n_out, h, w, epi, form, FUSED_ENCODER)
+        m = plan[0] if form is None else form
         if m:
             y = out if out is not None else torch.empty((b, n_out, h, w), device=x.device, dtype=torch.float32)
             if out is not None:
                 assert out.shape == (b, n_out, h, w) and out.is_contiguous()
-            epi = 2 if (bias is not None or slope is not None) else 0
-            if m == K.FUSED:
-                if K.WINO_LOG is not None:
-                    K.WINO_LOG.append(f"conv3x3 (winograd F(4x4,3x3) fused) K {k} N {n_out} {h}x{w} B {b}")
-                call("w2e_wino_fused", ptr(x), ptr(in_scale), ptr(K._wino_weights_fused(wp, k, n_out)), ptr(out_scale), ptr(y), b, k, n_out, h, w,
-                     epi, None, None, ptr(bias), ptr(slope), None, None, K.FUSED_WGS, stream_ptr())
-            else:
-                K.wino_gemm_conv(x, wp, in_scale, out_scale, y, k, n_out, h, w, epi, None, None, bias, slope, tag="conv3x3")
+            K.wino_conv(m, x, wp, in_scale, out_scale, y, k, n_out, h, w, epi, None, None, bias, slope, tag="conv3x3", plan=plan)
             return y
     if out is not None:
         assert mode != K.MODE_UP and out.shape == (b, n_out, h, w) and out.is_contiguous()
