@@ -50,7 +50,9 @@ extern "C" {
  * Still 7, additive: w2e_adam_step (K13b) and w2e_rstyle_* (K12e, w2e_attention.h: the region-attention net's style branch); and
  * w2e_conv3x3_plan (the conv dispatcher's decision as a host-side query).
  * Still 7, although not additive: w2e_wino_plan (which form a stride-1 3x3 conv takes, and the GEMM form's tiles / K split / workspace)
- * supersedes w2e_wino_gemm_plan, which is gone.  As above: one caller, built from the same tree. */
+ * supersedes w2e_wino_gemm_plan, which is gone.  As above: one caller, built from the same tree.
+ * Still 7, additive: w2e_image_resize_plan / w2e_image_resize / w2e_image_quantize (w2e_image.h: Pillow-exact resize in,
+ * torchvision-exact bytes out). */
 #define W2E_VERSION 7
 
 int w2e_version(void);

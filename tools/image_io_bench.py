@@ -1,0 +1,196 @@
+"""Times the image I/O calls (where2edit_amd/image_io.py, csrc/image.hip) against what a user would otherwise run, and the captured
+config-5 pipeline with bytes at both ends against floats at both ends.
+
+  to_tensor   uint8 [B,1024,1024,3] -> fp32 [B,3,256,256]   vs  permute -> float -> F.interpolate(bilinear, antialias) -> / 255 -> normalise
+  label_ids   uint8 [B,512,512]     -> uint8 [B,64,64]      vs  float -> F.interpolate(bilinear, antialias) -> round -> uint8
+              (the stock pixels are close to Pillow's, not equal: the largest distance in grey levels / the share of differing ids is
+              reported, not asserted)
+              and, where PIL imports, Pillow's own resize (+ the numpy ToTensor / Normalize) on one host core
+  to_bytes    fp32 [B,3,1024,1024]  -> uint8 [B,1024,1024,3] (grid=False) and the make_grid canvas (grid=True)
+                                                            vs  the op sequence of torchvision 0.8.2's save_image on the device
+  pipeline    capture_invert_and_edit at batch 8, float in / float out against uint8 in / uint8 out, each with the device-to-host
+              copy of its images and mask into pinned memory
+
+HIP events around `--inner` back-to-back calls of the Python entry point, device-synchronised, after a warm-up; the variants of a
+group alternate, `--repeats` times each (>= 5): the median, with min .. max as the spread a difference has to exceed.  `bytes` is
+what the call has to move (input + output), GB/s = bytes / median.  One JSON line per (group, variant, batch), appended to --out.
+
+    python tools/image_io_bench.py [--repeats 20] [--inner 10] [--skip-pipeline] [--out profiles/image_io_bench.jsonl]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def stock_to_tensor(x, size, mean=0.5, std=0.5):
+    y = F.interpolate(x.permute(0, 3, 1, 2).float(), size=size, mode="bilinear", antialias=True, align_corners=False)
+    return y.div(255).sub_(mean).div_(std)
+
+
+def stock_label_ids(x, size):
+    y = F.interpolate(x[:, None].float(), size=size, mode="bilinear", antialias=True, align_corners=False)
+    return y.round_().clamp_(0, 255).to(torch.uint8)[:, 0]
+
+
+def stock_to_bytes(x, lo=-1.0, hi=1.0, nrow=8, padding=2, grid=True):
+    """torchvision 0.8.2 utils.save_image up to the byte tensor, on the device the images are on."""
+    t = x.clone()
+    t.clamp_(min=lo, max=hi)
+    t.add_(-lo).div_(hi - lo + 1e-5)
+    if not grid:
+        return t.mul(255).add_(0.5).clamp_(0, 255).permute(0, 2, 3, 1).to(torch.uint8).contiguous()
+    b, _, h, w = t.shape
+    if b == 1:
+        canvas = t[0]
+    else:
+        xmaps = min(nrow, b)
+        ymaps = -(-b // xmaps)
+        canvas = t.new_full((3, (h + padding) * ymaps + padding, (w + padding) * xmaps + padding), 0.0)
+        for k in range(b):
+            yy, xx = divmod(k, xmaps)
+            canvas.narrow(1, yy * (h + padding) + padding, h).narrow(2, xx * (w + padding) + padding, w).copy_(t[k])
+    return canvas.mul(255).add_(0.5).clamp_(0, 255).permute(1, 2, 0).to(torch.uint8).contiguous()
+
+
+def time_group(variants, repeats, inner):
+    """{name: [ms per call]}: the variants alternate; an interval is `inner` calls between two events."""
+    for fn in variants.values():
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    times = {n: [] for n in variants}
+    for _ in range(repeats):
+        for name, fn in variants.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(inner):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            times[name].append(e0.elapsed_time(e1) / inner)
+    return times
+
+
+def line(group, variant, batch, ms, nbytes, **extra):
+    med = statistics.median(ms)
+    out = {"tool": "image_io_bench", "group": group, "variant": variant, "batch": batch, "bytes": nbytes, "ms_median": med, "ms_min": min(ms),
+           "ms_max": max(ms), "repeats": len(ms), "gb_per_s": nbytes / med / 1e6}
+    out.update(extra)
+    return out
+
+
+def pillow_ms(x_host, size, label, repeats=5):
+    """Median ms per IMAGE of Pillow's resize (+ ToTensor / Normalize in numpy for images) on this process' one thread, or None."""
+    try:
+        import numpy as np
+        from PIL import Image
+    except ImportError:
+        return None
+    img = Image.fromarray(x_host[0].numpy(), "L" if label else "RGB")
+    ms = []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        r = np.asarray(img.resize((size, size), getattr(Image, "Resampling", Image).BILINEAR))
+        if not label:
+            r = (r.transpose(2, 0, 1).astype(np.float32) / np.float32(255) - np.float32(0.5)) / np.float32(0.5)
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(ms)
+
+
+def bench_calls(a, lines):
+    from where2edit_amd import image_io as I
+    dev = "cuda"
+    g = torch.Generator().manual_seed(0)
+    for b in (1, 8):
+        img = torch.randint(0, 256, (b, 1024, 1024, 3), generator=g, dtype=torch.uint8)
+        lab = torch.randint(0, 19, (b, 16, 16), generator=g, dtype=torch.uint8).repeat_interleave(32, 1).repeat_interleave(32, 2).contiguous()
+        img_d, lab_d = img.to(dev), lab.to(dev)
+        ours, stock = I.to_tensor(img_d, 256), stock_to_tensor(img_d, (256, 256))
+        differ_img = float((ours - stock).abs().max()) * 127.5  # in grey levels: Normalize(0.5, 0.5) maps one level to 1 / 127.5
+        differ_lab = float((I.label_ids(lab_d, 64) != stock_label_ids(lab_d, (64, 64))).float().mean())
+        nb_img, nb_lab = img.numel() + b * 3 * 256 * 256 * 4, lab.numel() + b * 64 * 64
+        t = time_group({"hip": lambda: I.to_tensor(img_d, 256), "stock": lambda: stock_to_tensor(img_d, (256, 256))}, a.repeats, a.inner)
+        lines.append(line("to_tensor_1024_256", "hip", b, t["hip"], nb_img))
+        lines.append(line("to_tensor_1024_256", "stock", b, t["stock"], nb_img, max_grey_levels_from_hip=differ_img))
+        t = time_group({"hip": lambda: I.label_ids(lab_d, 64), "stock": lambda: stock_label_ids(lab_d, (64, 64))}, a.repeats, a.inner)
+        lines.append(line("label_ids_512_64", "hip", b, t["hip"], nb_lab))
+        lines.append(line("label_ids_512_64", "stock", b, t["stock"], nb_lab, values_differing_from_hip=differ_lab))
+        if b == 1:
+            for group, x, size, label, nbytes in (("to_tensor_1024_256", img, 256, False, nb_img), ("label_ids_512_64", lab, 64, True, nb_lab)):
+                ms = pillow_ms(x, size, label)
+                if ms is not None:
+                    lines.append(line(group, "pillow_one_host_core_per_image", 1, [ms], nbytes))
+        x = (torch.rand(b, 3, 1024, 1024, generator=g) * 2.2 - 1.1).to(dev)
+        for grid in (False, True):
+            ours, stock = I.to_bytes(x, grid=grid), stock_to_bytes(x, grid=grid)
+            differ = float((ours != stock).float().mean()) if ours.shape == stock.shape else 1.0
+            nb = x.numel() * 4 + ours.numel()
+            t = time_group({"hip": lambda: I.to_bytes(x, grid=grid), "stock": lambda: stock_to_bytes(x, grid=grid)}, a.repeats, a.inner)
+            group = "to_bytes_1024_grid" if grid else "to_bytes_1024"
+            lines.append(line(group, "hip", b, t["hip"], nb))
+            lines.append(line(group, "stock", b, t["stock"], nb, values_differing_from_hip=differ))
+        del x, img_d, lab_d
+
+
+def bench_pipeline(a, lines, batch=8):
+    import bench  # build_config5: the modules and inputs of the config-5 benchmark
+    from where2edit_amd.demo_pipeline import capture_invert_and_edit
+    dev = torch.device("cuda")
+    imgs, e4e, g, clip, net, text, att = bench.build_config5(dev, batch, 0)
+    gen = torch.Generator().manual_seed(5)
+    u8 = torch.randint(0, 256, (batch, 1024, 1024, 3), generator=gen, dtype=torch.uint8).to(dev)
+    run_f = capture_invert_and_edit(imgs, e4e, g, clip, net, text, att, attention_layer=13)
+    run_b = capture_invert_and_edit(u8, e4e, g, clip, net, text, att, attention_layer=13, as_bytes=True)
+    keys_f, keys_b = ("img_orig", "img_gen", "mask"), ("img_orig_u8", "img_gen_u8", "mask_u8")
+    out_f, out_b = run_f(imgs, text, att), run_b(u8, text, att)
+    pinned = {k: torch.empty(out.shape, dtype=out.dtype, pin_memory=True) for o, keys in ((out_f, keys_f), (out_b, keys_b)) for k, out in
+              ((k, o[k]) for k in keys)}
+
+    def step(run, x, keys):
+        out = run(x, text, att)
+        for k in keys:
+            pinned[k].copy_(out[k], non_blocking=True)
+
+    t = time_group({"float_in_float_out": lambda: step(run_f, imgs, keys_f), "uint8_in_uint8_out": lambda: step(run_b, u8, keys_b)}, a.repeats, 1)
+    for name, x, keys in (("float_in_float_out", imgs, keys_f), ("uint8_in_uint8_out", u8, keys_b)):
+        d2h = sum(pinned[k].numel() * pinned[k].element_size() for k in keys)
+        med = statistics.median(t[name])
+        lines.append(line("config5_captured_with_d2h", name, batch, t[name], d2h, images_per_s=batch / med * 1e3, input_bytes=x.numel() * x.element_size(),
+                          d2h_bytes=d2h))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=20)
+    ap.add_argument("--inner", type=int, default=10)
+    ap.add_argument("--skip-pipeline", action="store_true")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "image_io_bench.jsonl"))
+    a = ap.parse_args()
+    if a.repeats < 5:
+        raise SystemExit("--repeats must be >= 5: the spread is part of the result")
+    if not torch.cuda.is_available():
+        raise SystemExit("image_io_bench needs the GPU: a host timing says nothing about these kernels")
+    lines = []
+    with torch.no_grad():
+        bench_calls(a, lines)
+        if not a.skip_pipeline:
+            bench_pipeline(a, lines)
+    for ln in lines:
+        print(json.dumps(ln))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            for ln in lines:
+                f.write(json.dumps(ln) + "\n")
+
+
+if __name__ == "__main__":
+    main()

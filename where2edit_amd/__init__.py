@@ -19,6 +19,8 @@ Layout:
                           style branch as one node on csrc/region_style.hip, `Adam` = torch.optim.Adam's rule as one launch
   dist.py                 data-parallel step: shard latents, one RCCL all-reduce of mapper grads
   evaluation.py           the region mask's IoU against parsing labels (utils.py:639-726): MaskIoU, calculate_iou
+  image_io.py             bytes in, bytes out on csrc/image.hip: Pillow's resize + ToTensor / Normalize (to_tensor, label_ids, resize_u8),
+                          torchvision's save_image up to the PNG encoder (to_bytes)
 """
 __version__ = "0.1.0"
 
@@ -58,6 +60,7 @@ def r1_penalty(discriminator, real, return_logits=False):
 
 # where2edit_amd.evaluation's public names, importable from the package (resolved on first use: importing the package stays light)
 _EVALUATION = ("CELEBAMASK_REGIONS", "region_lut", "binarise", "attention_with_text", "MaskIoU", "calculate_iou")
+_IMAGE_IO = ("resample_tables", "resize_u8", "to_tensor", "label_ids", "to_bytes")
 
 
 def __getattr__(name):
@@ -67,4 +70,7 @@ def __getattr__(name):
     if name in _EVALUATION:
         from . import evaluation
         return getattr(evaluation, name)
+    if name in _IMAGE_IO:
+        from . import image_io
+        return getattr(image_io, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -81,6 +81,10 @@ _PROTOS = {
     "w2e_mask_blend_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "w2e_mask_blend_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "w2e_mask_iou_counts": (_I, [_P, _P, _P, _F, _I, _I, _I, _P, _P]),  # include/w2e_attention.h (evaluation.py)
+    # include/w2e_image.h (image_io.py)
+    "w2e_image_resize_plan": (_I, [_I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int64)]),
+    "w2e_image_resize": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P]),
+    "w2e_image_quantize": (_I, [_P, _I, _I, _I, _I, _F, _F, _F, _I, _I, _F, _I, _P, _P]),
 }
 
 _lib = None

@@ -10,7 +10,11 @@
     G(new codes, blend at attention_layer under the mask)  -> edited image                (:156)
     CLIP image features of the edited image                                               (try_demo.py:148-149)
 
-No backward anywhere; every rank of an N-GPU run processes its own images (replicas only)."""
+No backward anywhere; every rank of an N-GPU run processes its own images (replicas only).
+
+Both ends may be bytes (image_io.py): a uint8 [B,H,W,3] batch of any size goes through Pillow's resize + ToTensor + Normalize on the
+device (try_demo.py:96-99), and as_bytes=True adds the images as the bytes torchvision's save_image would encode (4x fewer bytes to
+copy to the host than the fp32 images)."""
 import torch
 import torch.nn.functional as F
 
@@ -29,10 +33,17 @@ def gaussian_blur5(x):
 
 @torch.no_grad()
 def invert_and_edit(images, e4e, g_ema, clip_loss, mapper, text_features, attention_text_features, *, attention_layer=13,
-                    strength_alpha=0.1, attention_threshold=0.8):
-    """images [B,3,256,256] in [-1,1]; text_features / attention_text_features [B,512] (CLIP text embeddings; the
-    reference tokenises with OpenAI's BPE, which is not in this image).  Returns a dict with img_orig, img_gen, the
-    mask, the inverted W+ and the new S codes, and the CLIP image features before / after."""
+                    strength_alpha=0.1, attention_threshold=0.8, as_bytes=False):
+    """images [B,3,256,256] in [-1,1], or uint8 [B,H,W,3] of any size (decoded RGB images: they go through
+    image_io.to_tensor(images, 256), the reference's Resize((256, 256)) + ToTensor + Normalize(0.5, 0.5) with Pillow's own pixel
+    values); text_features / attention_text_features [B,512] (CLIP text embeddings; the reference tokenises with OpenAI's BPE, which
+    is not in this image).  Returns a dict with img_orig, img_gen, the mask, the inverted W+ and the new S codes, and the CLIP
+    image features before / after.  as_bytes=True adds img_orig_u8 / img_gen_u8, uint8 [B,1024,1024,3] = image_io.to_bytes(img,
+    (-1, 1), grid=False), the bytes of save_image(normalize=True, range=(-1, 1)) for each image on its own, and mask_u8, uint8
+    [B,s,s,1] = to_bytes(mask, (0, 1), grid=False)."""
+    if images.dtype == torch.uint8:
+        from .image_io import to_tensor
+        images = to_tensor(images, 256)
     b = images.shape[0]
     latents = e4e(images)
     if hasattr(g_ema, "style_codes"):  # the codes alone: the reference runs the whole generator here and drops the image
@@ -54,15 +65,22 @@ def invert_and_edit(images, e4e, g_ema, clip_loss, mapper, text_features, attent
     img_gen, _, _, _ = g_ema([new_codes], input_is_latent=True, randomize_noise=False, return_features=True, input_is_stylespace=True,
                              attention_layer=attention_layer, attention_map=mask, feature_map=feats)
     feat_gen = clip_loss.model.encode_image(clip_loss.preprocess(img_gen))
-    return {"img_orig": img_orig, "img_gen": img_gen, "mask": mask, "latents": latents, "new_codes": new_codes,
-            "features_orig": feat_orig, "features_gen": feat_gen}
+    out = {"img_orig": img_orig, "img_gen": img_gen, "mask": mask, "latents": latents, "new_codes": new_codes,
+           "features_orig": feat_orig, "features_gen": feat_gen}
+    if as_bytes:
+        from .image_io import to_bytes
+        out["img_orig_u8"], out["img_gen_u8"] = to_bytes(img_orig, (-1, 1), grid=False), to_bytes(img_gen, (-1, 1), grid=False)
+        out["mask_u8"] = to_bytes(mask, (0, 1), grid=False)
+    return out
 
 
 def capture_invert_and_edit(images, e4e, g_ema, clip_loss, mapper, text_features, attention_text_features, *, warmup=3, **kw):
     """The fixed-shape pipeline as ONE hipGraph: returns `run(images, text_features, attention_text_features) -> dict` that copies
     the inputs into static buffers, replays the graph and returns the (static) output tensors.  About 1500 launches per call are
     otherwise enqueued eagerly and the pipeline is host-bound (40 ms of kernels in 52 ms of wall time at batch 8).  As for
-    Coach.capture_step, a pipeline that issues memset operations is refused (they are not replayed reliably on this ROCm stack)."""
+    Coach.capture_step, a pipeline that issues memset operations is refused (they are not replayed reliably on this ROCm stack).
+    `images` may be uint8 [B,H,W,3] (the static buffer is then bytes, and `run` takes bytes of that shape) and as_bytes=True is
+    passed on: the warm-up runs fill image_io's table caches, so the captured resize and quantise kernels copy nothing."""
     static = [images.clone(), text_features.clone(), attention_text_features.clone()]
 
     def body():

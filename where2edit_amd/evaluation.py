@@ -9,7 +9,8 @@ streaming kernel (`w2e_mask_iou_counts`: binarisation, label remap and the three
 [T,3] int64 table on the device).  Nothing moves to the host before `MaskIoU.compute()`, which copies 3*T integers.
 
 Callers bring the dataset: `(image or W+ latent, parsing label already resized to the mask's S x S)` pairs, and the CLIP text
-features of the prompts (there is no tokeniser in this package)."""
+features of the prompts (there is no tokeniser in this package).  Decoded bytes are welcome too: uint8 [B,H,W,3] images and, with
+`calculate_iou(label_resize=...)`, uint8 labels of any size are resized on the device with Pillow's own arithmetic (image_io.py)."""
 import ctypes
 
 import torch
@@ -176,9 +177,15 @@ def attention_with_text(net, text_features, codes, feature_map, attention_layer)
 
 @torch.no_grad()
 def calculate_iou(samples, g_ema, mapper, text_features, *, attention_layer=13, e4e=None, max_images=90, threshold=0.8,
-                  work_in_stylespace=True, mapping=None):
-    """utils.py:654-726.  `samples` yields (x, label): x = [B,3,256,256] images (then `e4e`, e.g. psp_encoders.load_e4e_standalone's,
-    is required) or, with e4e=None, W+ latents [B,n_latent,512]; label = the parsing label at the mask's resolution (MaskIoU.update).
+                  work_in_stylespace=True, mapping=None, label_resize=None):
+    """utils.py:654-726.  `samples` yields (x, label): x = [B,3,256,256] images or uint8 [B,H,W,3] decoded images of any size (they go
+    through image_io.to_tensor(x, 256) = transform_img(256, ...); for both `e4e`, e.g. psp_encoders.load_e4e_standalone's, is
+    required) or, with e4e=None, W+ latents [B,n_latent,512]; label = the parsing label at the mask's resolution (MaskIoU.update).
+    label_resize: None -- labels come at the mask's S x S (a mismatch is MaskIoU.update's error); "bilinear" / "nearest" -- labels are
+    uint8 ids [B,H,W] or [B,1,H,W] of any size and are resized to S x S by image_io.label_ids.  "bilinear" is the REFERENCE-EXACT
+    choice: transform_label resizes the mode-L label PNG with Pillow's antialiased bilinear filter, so ids blend at region borders
+    (a pixel between skin = 1 and hair = 13 gets some id in between, e.g. 7 = r_brow) and `label == k` keeps only the exact hits;
+    use it to reproduce the reference's numbers.  "nearest" is the sensible choice: every pixel keeps an id that was there.
     text_features [T,512]: the CLIP text features of the T prompts (CELEBAMASK_REGIONS lists the reference's eight), one region each;
     `mapping` as for MaskIoU (a T other than 8 needs its own).  Stops after `max_images` images (the reference: 90 batches of 1).
     Returns (per-region IoU, mean IoU).  One generator pass with features per batch, one mask-branch pass per prompt over the same
@@ -186,6 +193,8 @@ def calculate_iou(samples, g_ema, mapper, text_features, *, attention_layer=13, 
     if not text_features.is_floating_point():
         raise RuntimeError("calculate_iou: text_features are the CLIP text features [T,512] of the prompts; encode token ids with the "
                            "CLIP model's encode_text first")
+    if label_resize not in (None, "bilinear", "nearest"):
+        raise ValueError(f"calculate_iou: label_resize is None, 'bilinear' or 'nearest' (got {label_resize!r})")
     dev = text_features.device
     n_prompts = text_features.shape[0]
     metric = MaskIoU(classes=n_prompts, threshold=threshold, mapping=mapping, device=dev)
@@ -196,6 +205,11 @@ def calculate_iou(samples, g_ema, mapper, text_features, *, attention_layer=13, 
             break
         x, label = x[:max_images - seen].to(dev, non_blocking=True), label[:max_images - seen].to(dev, non_blocking=True)
         batch = x.shape[0]
+        if x.dtype == torch.uint8:
+            if e4e is None:
+                raise RuntimeError(f"calculate_iou: uint8 samples of shape {tuple(x.shape)} are decoded images [B,H,W,3]: pass e4e=...")
+            from .image_io import to_tensor
+            x = to_tensor(x, 256)
         if e4e is not None:
             w = e4e(x)
         elif x.ndim == 3:
@@ -212,6 +226,11 @@ def calculate_iou(samples, g_ema, mapper, text_features, *, attention_layer=13, 
         size = feats[attention_layer - 1].shape[-1]
         n_codes = _codes_dims(codes)[1]
         masks = torch.cat([mapper.mask(feats, size, text_features[j:j + 1].repeat(batch, 1), n_codes) for j in range(n_prompts)], 1)
+        if label_resize is not None:
+            from .image_io import label_ids
+            if label.ndim == 4 and label.shape[1] == 1:
+                label = label[:, 0]
+            label = label_ids(label.contiguous(), size, label_resize)
         metric.update(masks, label)  # (binarisation happens inside the counting kernel)
         seen += batch
     return metric.compute()
