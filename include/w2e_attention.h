@@ -66,7 +66,9 @@ int w2e_kmeans_reduce(const float* partial, int rows, int n, double* acc, void* 
 /* One source = one cached activation and the 1x1 StyledConv(C, 32, 1, C) applied to it with a style given in S-space:
  *   a[b,o,p] = lrelu( d[b,o] * sum_i wscaled[o,i] * s[b,i] * feat[b,i,src(p)] + nw*noise[b,p] + bias[o] ) * sqrt2
  * evaluated only at the `size` x `size` pixels p that F.interpolate(., size) (nearest) would keep / replicate:
- * src(y,x) = (floor(y*res/size), floor(x*res/size)).  wscaled = scale*W [32,C];  d = the demodulation coefficients
+ * src(y,x) = (n(y), n(x)), n(t) = min(floor(t * ((float)res / (float)size)), res - 1) evaluated in fp32, as torch does (the
+ * exact-integer floor(t*res/size) differs at some ratios that are no power of two).  w2e_cluster_pool and both backward entry
+ * points read through the same index.  wscaled = scale*W [32,C];  d = the demodulation coefficients
  * [B,32]; noise [B,size*size] or NULL (NoiseInjection draws randn when no noise is passed: i.i.d., so drawing it
  * at the kept pixels is the same distribution), nw = device scalar noise strength. */
 typedef struct {

@@ -9,12 +9,12 @@ import os
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 import make_golden_attention as M
 import mask_train_common as C
 import seeded
 from helpers import assert_close, assert_grad_close, golden, rel_err
+from mask_ref import logits_ref as _logits_ref, nearest_index, pool_ref as _pool_ref
 from oracle import attention_net as OA
 
 pytestmark = pytest.mark.gpu
@@ -30,47 +30,19 @@ def _close(a, b, what):
 
 
 # ---------------------------------------------------------------------------------------------------- kernel level
-def _pool_ref(each, assign, size, clusters):
-    """run_attention.py:843-884 in the dtype of `each`: same / loss_reg / loss_tv / final of oracle/attention_net.py:99-113, with an
-    assignment given at its own resolution (nearest resize) that may hold ids outside [0, K)."""
-    b, cs = each.shape[0], assign.shape[1]
-    idx = (torch.arange(size) * cs) // size
-    choice = assign.long()[:, idx][:, :, idx]
-    same = torch.ones_like(each)
-    loss_reg = each.new_zeros(1)
-    for bb in range(b):
-        for k in range(clusters):
-            m = choice[bb] == k
-            if m.any():
-                mean = each[bb][m].mean()
-                full = torch.zeros_like(choice, dtype=torch.bool)
-                full[bb] = m
-                same = torch.where(full, mean, same)
-                loss_reg = loss_reg + torch.relu(mean - 0.7)
-    loss_reg = loss_reg / float(b)
-    loss_tv = F.mse_loss(each, same.detach())
-    amap = same.unsqueeze(1)
-    thr = torch.where(amap < 0.8, amap - amap.detach(), amap)
-    prev = torch.get_default_dtype()
-    torch.set_default_dtype(each.dtype)
-    try:
-        final = OA.gaussian_blur5(thr)
-    finally:
-        torch.set_default_dtype(prev)
-    return final, loss_reg, loss_tv, same
-
-
-@pytest.mark.parametrize("size,cs,clusters,batch", [(16, 16, 6, 2), (20, 8, 5, 3), (64, 64, 20, 2), (7, 3, 4, 1)])
+@pytest.mark.parametrize("size,cs,clusters,batch", [(16, 16, 6, 2), (20, 8, 5, 3), (64, 64, 20, 2), (7, 3, 4, 1), (22, 26, 7, 2), (46, 14, 5, 1),
+                                                    (128, 64, 32, 1)])
 def test_cluster_pool_bwd_vs_float64(size, cs, clusters, batch):
     """An empty cluster (id clusters-1 is never assigned), out-of-range ids (-1 and K), the reflect borders (r is dense up to the
     edge; size 7 folds every tap), `size` not a multiple of the cluster resolution (20 / 8, 7 / 3), means on both sides of 0.7 and
-    0.8."""
+    0.8; 26 -> 22 and 14 -> 46, where torch's nearest resize (the reference's gather, mask_ref.nearest_index) and floor(dst * in / out)
+    read different pixels; size 128, the 128 KB LDS opt-in."""
     from where2edit_amd.run_attention import _ClusterPoolTrain
     rs = np.random.RandomState(size * 100 + cs)
     assign = torch.from_numpy(rs.randint(0, clusters - 1, size=(batch, cs, cs)).astype(np.int32))
     assign[0, 0, 0], assign[-1, cs - 1, cs - 2] = -1, clusters
     level = torch.tensor([0.75, 0.55, 0.85, 0.65, 0.95])[assign.long().clamp(0, clusters - 1) % 5]
-    idx = (torch.arange(size) * cs) // size
+    idx = nearest_index(cs, size)
     each = (level[:, idx][:, :, idx] + 0.04 * seeded.tensor(f"pool.each{size}", (batch, size, size))).clamp(0.01, 0.99)
     r = seeded.tensor(f"pool.r{size}", (batch, 1, size, size))
     e64 = each.double().requires_grad_(True)
@@ -96,27 +68,12 @@ def test_cluster_pool_bwd_vs_float64(size, cs, clusters, batch):
         _close(g, g_o, "g_each, " + name)
 
 
-def _logits_ref(feats, per, wl, s_last, bias_last, nw_last, initial_bias, noises, size, eps):
-    """include/w2e_attention.h's formulas in the dtype of the inputs (float64 in the tests), on stock ops."""
-    b, acts = s_last.shape[0], []
-    for j, f in enumerate(feats):
-        wsc, style, bias, nw = per[4 * j:4 * j + 4]
-        idx = (torch.arange(size) * f.shape[2]) // size
-        g = f[:, :, idx][:, :, :, idx].reshape(b, f.shape[1], -1)
-        m = torch.einsum("io,bi,bip->bop", wsc, style, g)
-        d = torch.rsqrt((wsc[None] * style[:, :, None]).square().sum(1) + eps)
-        pre = m * d[:, :, None] + nw * noises[j][:, None, :] + bias[None, :, None]
-        acts.append(F.leaky_relu(pre, 0.2) * 2 ** 0.5)
-    a = torch.cat(acts, 1)
-    d_last = torch.rsqrt((s_last * wl).square().sum(1) + eps)
-    v = (a * (wl * s_last)[:, :, None]).sum(1) * d_last[:, None] + nw_last * noises[-1] + bias_last
-    return torch.sigmoid(F.leaky_relu(v, 0.2) * 2 ** 0.5 + initial_bias).reshape(b, size, size)
-
-
-@pytest.mark.parametrize("size,batch,shapes", [(16, 2, ((512, 4), (256, 32), (32, 16), (32, 64))), (12, 3, ((40, 5), (256, 48)))])
+@pytest.mark.parametrize("size,batch,shapes", [(16, 2, ((512, 4), (256, 32), (32, 16), (32, 64))), (12, 3, ((40, 5), (256, 48))),
+                                               (22, 3, ((40, 26), (8, 5)))])
 def test_attention_logits_bwd_vs_float64(size, batch, shapes):
     """Every output of w2e_attention_logits_bwd: channel counts 512 / 256 / 32 (and 40: not a multiple of the 32-channel chunk), source
-    resolutions below, at and above `size` (and 5 -> 12: a non-integer ratio), explicit non-zero noise and noise strengths."""
+    resolutions below, at and above `size` (and 5 -> 12: a non-integer ratio; 26 -> 22: a ratio at which torch's nearest resize and
+    floor(dst * in / out) read different pixels), explicit non-zero noise and noise strengths."""
     from where2edit_amd.run_attention import _MaskLogitsTrain
     n, eps = len(shapes), 1e-8
     t = lambda name, shape, scale=1.0, shift=0.0: seeded.tensor(f"logits{size}.{name}", shape, scale, shift)  # noqa: E731

@@ -181,8 +181,9 @@ __global__ __launch_bounds__(256) void att_source_kernel(const AttLaunch L) {
     const int pix = blockIdx.x * 256 + threadIdx.x;
     const bool live = pix < size * size;
     const int y = live ? pix / size : 0, x = live ? pix % size : 0;
-    // F.interpolate(mode='nearest') source index: floor(dst * in / out)
-    const int sy = (int)(((int64_t)y * R) / size), sx = (int)(((int64_t)x * R) / size);
+    // F.interpolate(mode='nearest') source index, in fp32 as torch does: min(floor(dst * ((float)in / out)), in - 1)
+    const float scale = (float)R / (float)size;
+    const int sy = nearest_src(y, scale, R), sx = nearest_src(x, scale, R);
     const float* f = s.feat + (int64_t)b * C * R * R + (int64_t)sy * R + sx;
     if (threadIdx.x < 32) {
         dcoef[threadIdx.x] = s.demod[b * 32 + threadIdx.x];
@@ -258,9 +259,10 @@ __global__ __launch_bounds__(256) void cluster_pool_kernel(const float* __restri
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float* e = each + (int64_t)b * npix;
     const int32_t* a = assign + (int64_t)b * csize * csize;
+    const float scale = (float)csize / (float)size;
     auto cluster_of = [&](int p) {
         const int y = p / size, x = p % size;
-        return a[(int)(((int64_t)y * csize) / size) * csize + (int)(((int64_t)x * csize) / size)];
+        return a[nearest_src(y, scale, csize) * csize + nearest_src(x, scale, csize)];
     };
     for (int k = 0; k < K; ++k) {
         float s = 0.f, n = 0.f;
@@ -425,7 +427,8 @@ extern "C" int w2e_cluster_pool(const float* each, const int32_t* assign, float*
     if (batch == 0) return 0;
     const size_t lds = sizeof(float) * 2 * (size_t)size * size;
     static unsigned done = 0;
-    if (lds > 64 * 1024) W2E_REQUIRE(big_lds_once((const void*)cluster_pool_kernel, &done), "cluster_pool: LDS opt-in failed");
+    // 128 KB at size 128, the most this kernel asks for: with its static arrays (part, kmean) a 160 KB opt-in is refused
+    if (lds > 64 * 1024) W2E_REQUIRE(big_lds_once((const void*)cluster_pool_kernel, &done, 128 * 1024), "cluster_pool: LDS opt-in failed");
     cluster_pool_kernel<<<batch, 256, lds, (hipStream_t)stream>>>(each, assign, same, means, counts, thr, final_map, size, csize,
                                                                  clusters, threshold);
     W2E_LAUNCH_CHECK("cluster_pool");

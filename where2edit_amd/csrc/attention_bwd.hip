@@ -162,6 +162,7 @@ __global__ __launch_bounds__(256) void att_bwd_contract_kernel(const AttBwdLaunc
     const int cg = lane >> 3, og = lane & 7;
     const int pl = threadIdx.x & (CT_PIX - 1), half = threadIdx.x >> 7;
     const int64_t plane = (int64_t)R * R;
+    const float scale = (float)R / (float)size;  // the forward's gather (att_source_kernel): torch's fp32 nearest index
     float acc[4][4];
 #pragma unroll
     for (int a = 0; a < 4; ++a)
@@ -171,7 +172,7 @@ __global__ __launch_bounds__(256) void att_bwd_contract_kernel(const AttBwdLaunc
         const int pix = p0 + pl;
         const bool live = pix < npix;
         const int y = live ? pix / size : 0, x = live ? pix % size : 0;
-        const int sy = (int)(((int64_t)y * R) / size), sx = (int)(((int64_t)x * R) / size);
+        const int sy = nearest_src(y, scale, R), sx = nearest_src(x, scale, R);
         const float* f = s.feat + ((int64_t)b * C + c0 + half * 16) * plane + (int64_t)sy * R + sx;
         const float* g = L.gm + (((int64_t)j * L.batch + b) * 32 + half * 16) * npix + (live ? pix : 0);
         float fv[16], gv[16];
@@ -257,9 +258,10 @@ __global__ __launch_bounds__(256) void cluster_pool_bwd_kernel(const float* __re
     const int b = blockIdx.x, npix = size * size;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int32_t* a = assign + (int64_t)b * csize * csize;
+    const float scale = (float)csize / (float)size;
     auto cluster_of = [&](int p) {
         const int y = p / size, x = p % size;
-        return a[(int)(((int64_t)y * csize) / size) * csize + (int)(((int64_t)x * csize) / size)];
+        return a[nearest_src(y, scale, csize) * csize + nearest_src(x, scale, csize)];
     };
     float* ga = lds;
     float* gb = lds + npix;
@@ -385,7 +387,8 @@ extern "C" int w2e_cluster_pool_bwd(const float* g_final, const float* each, con
     if (batch == 0) return 0;
     const size_t lds = sizeof(float) * 2 * (size_t)size * size;
     static unsigned done = 0;
-    if (lds > 64 * 1024) W2E_REQUIRE(big_lds_once((const void*)cluster_pool_bwd_kernel, &done), "cluster_pool_bwd: LDS opt-in failed");
+    // (128 KB at size 128: see w2e_cluster_pool)
+    if (lds > 64 * 1024) W2E_REQUIRE(big_lds_once((const void*)cluster_pool_bwd_kernel, &done, 128 * 1024), "cluster_pool_bwd: LDS opt-in failed");
     cluster_pool_bwd_kernel<<<batch, 256, lds, (hipStream_t)stream>>>(g_final, each, same, means, counts, assign, g_loss_reg, g_loss_tv,
                                                                      g_each, batch, size, csize, clusters);
     W2E_LAUNCH_CHECK("cluster_pool_bwd");

@@ -32,11 +32,16 @@ const Options& options();
 
 // Kernels that need more than 64 KB of dynamic LDS opt in once per (kernel, device).  Returns true when the current
 // device has the attribute set.  (hipFuncSetAttribute is per device: a process driving several GPUs needs it on each.)
-static inline bool big_lds_once(const void* fn, unsigned* done_mask) {
+// `bytes`: the most dynamic LDS the kernel will ever ask for.  The runtime refuses a request that, with the kernel's static
+// __shared__ arrays, exceeds the CU's 160 KB: a kernel that has any must pass its own, smaller bound.
+static inline bool big_lds_once(const void* fn, unsigned* done_mask, int bytes = 160 * 1024) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) return false;
     if (*done_mask & (1u << dev)) return true;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
+        (void)hipGetLastError();  // reported through the return value; not left for the next caller of the runtime to trip over
+        return false;
+    }
     *done_mask |= 1u << dev;
     return true;
 }

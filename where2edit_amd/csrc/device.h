@@ -46,6 +46,15 @@ __device__ __forceinline__ float quad_max(float v) {
 
 __device__ __forceinline__ float4 add4(const float4 a, const float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 
+// F.interpolate(mode='nearest') source index, as torch computes it: in fp32, with scale = (float)in / (float)out.  The exact-integer
+// floor(dst * in / out) reads a neighbouring pixel at some ratios that are no power of two (26 -> 22: destination 11).  Used by the
+// mask blend (elementwise.hip) and by every gather of the region-attention mask kernels (attention.hip, attention_bwd.hip).
+__device__ __forceinline__ int nearest_src(int dst, float scale, int in_size) {
+    // torch nearest: min(floor(dst * (in/out)), in-1)  (attention_model.py:548 uses the default mode)
+    const int s = (int)floorf(dst * scale);
+    return s < in_size - 1 ? s : in_size - 1;
+}
+
 __device__ __forceinline__ float quick_gelu(float x) { return x / (1.f + __expf(-1.702f * x)); }
 __device__ __forceinline__ float quick_gelu_grad(float x) {
     const float s = 1.f / (1.f + __expf(-1.702f * x));

@@ -135,12 +135,6 @@ __global__ void bias_act_bwd_reduce_kernel(const float* __restrict__ gy, const f
 }
 
 // ------------------------------------------------------------------------------------- K6
-__device__ __forceinline__ int nearest_src(int dst, float scale, int in_size) {
-    // torch nearest: min(floor(dst * (in/out)), in-1)  (attention_model.py:548 uses the default mode)
-    const int s = (int)floorf(dst * scale);
-    return s < in_size - 1 ? s : in_size - 1;
-}
-
 __global__ void mask_blend_fwd_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                       const float* __restrict__ mask, float* __restrict__ out, int64_t total, int C,
                                       int H, int W, int ms) {
