@@ -52,7 +52,9 @@ extern "C" {
  * Still 7, although not additive: w2e_wino_plan (which form a stride-1 3x3 conv takes, and the GEMM form's tiles / K split / workspace)
  * supersedes w2e_wino_gemm_plan, which is gone.  As above: one caller, built from the same tree.
  * Still 7, additive: w2e_image_resize_plan / w2e_image_resize / w2e_image_quantize (w2e_image.h: Pillow-exact resize in,
- * torchvision-exact bytes out). */
+ * torchvision-exact bytes out).
+ * Still 7, additive: w2e_upfirdn2d_plan / w2e_upfirdn2d_planar_ok / w2e_blur_adjoint_actbwd_plan (the FIR dispatcher's decisions as
+ * host-side queries). */
 #define W2E_VERSION 7
 
 int w2e_version(void);
@@ -68,7 +70,8 @@ const char* w2e_last_error(void);
  *   "tune_upall", "tune_dma", "tune_fuse", "tune_upblur", "tune_rgbfold", "tune_print", "tune_blur", "tune_gemm_s": kernel-selection aids -- they
  *   choose between kernels / tiles that compute the same result ("tune_blur": only bit 8, keep the LDS-tile FIR kernels
  *   for wide images; its bits 1/2/4 and "tune_skip" / "tune_clock" drop loads, arithmetic or stores, or synchronise,
- *   and are compiled in ONLY by -DW2E_TUNING: the shipped library ignores them)
+ *   and are compiled in ONLY by -DW2E_TUNING: the shipped library ignores them; "tune_fuse": 0 = the two-kernel form of the
+ *   up-sampling StyledConv backward, read by w2e_blur_adjoint_actbwd_plan)
  *   "debug_poison" [W2E_DEBUG_POISON] "1": host-side aid -- gradient rows the merged forward declares unused are
  *   filled with NaN instead of being left unwritten, so that a consumer that reads them fails loudly (tests)
  * w2e_get_option reads "conv_precision", "deterministic", "tune_cfg", "tune_upblur", "tune_rgbfold", "tuning_build" (1 = compiled with -DW2E_TUNING). */
@@ -106,6 +109,33 @@ int w2e_upfirdn2d(const float* x, const float* kern, float* y, int64_t planes, i
  * never written.  gy, y_fwd [planes, h, w]; noise [h*w] or NULL; w >= 256 and a multiple of 4; not in deterministic mode. */
 int w2e_blur_adjoint_actbwd(const float* gy, const float* y_fwd, const float* noise, const float* kern, float* gt, float* sums,
                             int64_t planes, int h, int w, float slope, float gain, void* stream);
+
+/* What the dispatcher of w2e_upfirdn2d would decide for a launch, after the library's current options (host code, no GPU: the decision
+ * looks at the scalar arguments, at how far x and y are from 16-byte alignment and at the options, never at a tensor).  The arguments
+ * are w2e_upfirdn2d's own (pad_y0 and flip select nothing); x_misalign / y_misalign = (uintptr_t)x & 15, (uintptr_t)y & 15.
+ * out[W2E_FIR_PLAN_FIELDS] = kernel (W2E_FIR_*), act, planar (the template flags, as the "upfirdn variant" line of tune_print reports
+ * them), grid (workgroups; 0 for an empty launch), block (threads), lds (dynamic bytes), and the kernel's three scalar arguments:
+ * (tiles_x, tiles_y, magic) for TILE / TILE4, (tiles_x, tiles_y, 0) for BLUR4, (col_groups, strips, 0) for STREAM4, (total, 0, 0) for
+ * GENERIC / DOWN4.  A launch the dispatcher refuses (a bad size, a tensor too large, a planar source it has no kernel for or with another
+ * row pitch) returns non-zero with the launch's own w2e_last_error() text. */
+#define W2E_FIR_GENERIC 0
+#define W2E_FIR_DOWN4 1
+#define W2E_FIR_TILE 2
+#define W2E_FIR_TILE4 3
+#define W2E_FIR_BLUR4 4
+#define W2E_FIR_STREAM4 5
+#define W2E_FIR_PLAN_FIELDS 9
+int w2e_upfirdn2d_plan(int64_t planes, int in_h, int in_w, int out_h, int out_w, int kh, int kw, int up, int down, int pad_x0,
+                       int in_layout, int in_pitch, int act, int x_misalign, int y_misalign, int64_t* out);
+/* 1 where w2e_upfirdn2d accepts in_layout = 1 (the phase-planar source) for these taps, up / down and output width, else 0: the rule by
+ * which the launcher refuses the layout, for callers that hold a planar image and must choose between handing it over and
+ * re-interleaving it first. */
+int w2e_upfirdn2d_planar_ok(int kh, int kw, int up, int down, int out_w);
+/* Whether the library takes the activation backward + adjoint blur of a [planes, h, w] gradient with kh x kw taps as ONE pass
+ * (w2e_blur_adjoint_actbwd): *fused = 1 where that launcher accepts the shape (4x4 taps, a width >= 256 that is a multiple of 4, the
+ * plane and grid limits), the library is not in deterministic mode and the option tune_fuse is not 0; else 0 (the caller then runs
+ * w2e_bias_act_bwd_reduce + w2e_upfirdn2d).  The launcher itself does not read tune_fuse: a direct call runs whatever the option says. */
+int w2e_blur_adjoint_actbwd_plan(int64_t planes, int h, int w, int kh, int kw, int* fused);
 
 /* ---- K3  bias (+noise) + leaky-relu * gain  (op/fused_act.py:23-39, model.py:285-290) -----
  * x viewed as [outer, channels, inner]; bias[channels] or NULL; noise[inner] or NULL with device

@@ -228,6 +228,7 @@ for _a in (0, 1):
 FIR_MATRIX += [
     E("stream4", 1, 1, (1, 2), (1025, 1025), (1024, 1024), (1, 1)),            # a real layer, once
     E("stream4", 0, 0, (1, 2), (130, 1024), (131, 1025), (2, 2)),
+    E("generic", 0, 0, (2, 3), (8, 8), (16, 16), (2, 2), up=2),                # the RGB-skip Upsample below 32 columns (8^2 -> 16^2)
 ]
 
 # stream4<ACTBWD> through w2e_blur_adjoint_actbwd: (samples, channels), h, w, with noise
@@ -584,6 +585,60 @@ def test_bad_arguments_are_refused_before_any_launch(w2e_opt, capfd):
     with pytest.raises(RuntimeError, match="deterministic mode"):
         call("w2e_blur_adjoint_actbwd", ptr(gy), ptr(yf), None, ptr(k4), ptr(gt), ptr(sums), 2, 8, 256, SLOPE, GAIN, stream_ptr())
     _no_variant_line(capfd)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("h,fusable", [(128, True), (64, False)], ids=["128-to-256", "64-to-128"])
+def test_styledconv_backward_takes_the_planned_form(h, fusable, w2e_opt, capfd):
+    """One up-sampling styled_conv (B 2, 8 -> 8 channels, h^2 -> (2h)^2) backward under the default options, tune_fuse = 0 and
+    deterministic = 1: the variant lines of the backward show the form w2e_blur_adjoint_actbwd_plan answers -- at 256 columns (the
+    narrowest the fused pass takes) one stream4<ACTBWD> launch and no separate adjoint blur by default, the unfused pair (an
+    `actbwd 0` adjoint blur onto 2h + 1) under the other two; at 128 columns the unfused pair under all three.  The input and style
+    gradients of the three agree to the figures tests/test_gpu_parity.py holds the fused pass to against the unfused pair
+    (test_blur_adjoint_with_fused_activation_backward: 2e-6 for the image-sized gradient, 2e-5 for what the sums feed)."""
+    from helpers import rel_err
+    from where2edit_amd import functional as K
+    b, k, n = 2, 8, 8
+    g = torch.Generator().manual_seed(31 + h)
+    wt = torch.randn(n, k, 3, 3, generator=g).to(DEV)
+    scale = 1.0 / math.sqrt(k * 9)
+    packs = (K.conv_pack(wt, scale, False, False), K.conv_pack(wt, scale, True, False))
+    wsq = (wt * scale).square().sum((2, 3)).contiguous()
+    kernel = seeded.fir_kernel(gain=4.0).to(DEV)
+    noise = torch.randn(1, 1, 2 * h, 2 * h, generator=g).to(DEV)
+    nw, bias = torch.full((1,), 0.3, device=DEV), (0.1 * torch.randn(n, generator=g)).to(DEV)
+    cot = torch.randn(b, n, 2 * h, 2 * h, generator=g).to(DEV)
+    x0, s0 = torch.randn(b, k, h, h, generator=g).to(DEV), (torch.rand(b, k, generator=g) + 0.5).to(DEV)
+
+    def run(option, value):
+        if option:
+            w2e_opt(option, value)
+        want_fused = fusable and option is None
+        assert K._blur_actbwd_planned(b * n, 2 * h, 2 * h, kernel.shape) == want_fused
+        x, s = x0.clone().requires_grad_(True), s0.clone().requires_grad_(True)
+        out = K.styled_conv(x, s, wsq, noise, nw, bias, packs, kernel, True)
+        torch.cuda.synchronize()
+        w2e_opt("tune_print", 1)
+        capfd.readouterr()
+        grads = torch.autograd.grad((out * cot).sum(), (x, s))
+        torch.cuda.synchronize()
+        lines = [m for ln in capfd.readouterr().err.splitlines() if (m := FIR_VARIANT.match(ln))]
+        w2e_opt("tune_print", 0)
+        if option:
+            w2e_opt(option, "" if option == "tune_fuse" else 0)
+        got = [(m[1], int(m[4]), int(m[12]), int(m[13])) for m in lines]  # kernel, actbwd, out_h, out_w
+        if want_fused:
+            assert got == [("stream4", 1, 2 * h + 1, 2 * h + 1)], got
+        else:
+            assert len(got) == 1 and got[0][1:] == (0, 2 * h + 1, 2 * h + 1), got
+        return grads
+
+    default, fuse0, det = run(None, None), run("tune_fuse", 0), run("deterministic", 1)
+    for name, other in (("tune_fuse = 0", fuse0), ("deterministic = 1", det)):
+        print(f"{2 * h}^2, default against {name}: input gradient {rel_err(default[0], other[0]):.2e}, style gradient {rel_err(default[1], other[1]):.2e}")
+    for name, other in (("tune_fuse = 0", fuse0), ("deterministic = 1", det)):
+        assert_close(default[0], other[0], 2e-6, f"input gradient, default against {name}")
+        assert_close(default[1], other[1], 2e-5, f"style gradient, default against {name}")
 
 
 @pytest.mark.gpu

@@ -521,7 +521,7 @@ def test_modconv_abi_non_square_and_ragged_channels(b, k, n, h, w):
     t, _ = K._modconv_raw(K.MODE_UP, x, up, s_in, s_out, h, w)
     ref_t = F.conv_transpose2d(xd, wt_t.double() * scale, stride=2) * so
     assert_close(K.unplanar(t, w), ref_t, FWD_TOL, "up")
-    if w >= 16:  # the 4x4 blur reading the phase-planar T directly (+ fused noise/bias/lrelu), and its plain-layout adjoint
+    if K.fir_planar_ok((4, 4), 2 * w):  # the 4x4 blur reading the phase-planar T directly (+ fused noise/bias/lrelu), and its plain-layout adjoint
         k4 = cu(seeded.fir_kernel(gain=4.0))
         noise2 = torch.randn(1, 1, 2 * h, 2 * w, generator=g).to(DEV)
         blurred = O.upfirdn2d(ref_t.float().cpu(), seeded.fir_kernel(gain=4.0), pad=(1, 1)).double().to(DEV)

@@ -73,7 +73,7 @@ class Problem:
         h, w = self.h, self.w
         t, _ = K._modconv_raw(K.MODE_UP, self.x, self.pack, self.s_in, self.s_out, h, w)
         act = (None,) + self.act(with_act)
-        if w >= 16:
+        if K.fir_planar_ok(self.kernel.shape, 2 * w):
             return K._upfirdn2d_raw(t, self.kernel, 2 * h, 2 * w, 1, 1, 1, 1, True, act=act, planar_hw=(2 * h + 1, 2 * w + 1))
         return K._upfirdn2d_raw(K.unplanar(t, w), self.kernel, 2 * h, 2 * w, 1, 1, 1, 1, True, act=act)
 

@@ -25,6 +25,9 @@ _PROTOS = {
     "w2e_get_option": (_I, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]),
     "w2e_upfirdn2d": (_I, [_P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _F, _F, _P]),
     "w2e_blur_adjoint_actbwd": (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _F, _F, _P]),
+    "w2e_upfirdn2d_plan": (_I, [_L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int64)]),
+    "w2e_upfirdn2d_planar_ok": (_I, [_I, _I, _I, _I, _I]),
+    "w2e_blur_adjoint_actbwd_plan": (_I, [_L, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int)]),
     "w2e_mapper_pixelnorm": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "w2e_mapper_linear": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _F, _F, _I, _I, _P]),
     "w2e_mapper_wgrad": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _F, _F, _I, _P]),

@@ -79,7 +79,7 @@ def blur(x):
 
 def blur_adjoint(t, h, w):
     """Adjoint of `blur` applied to the phase-planar UP output T [B,C,2,2,h/2+1,WP] of a [h+1,w+1] image: -> [B,C,h,w]."""
-    if w >= 32:  # the tile kernel reads the phase-planar layout directly
+    if K.fir_planar_ok((4, 4), w):  # the tile kernel reads the phase-planar layout directly
         return K._upfirdn2d_raw(t, _blur_kernel(t.device), h, w, 1, 1, 1, 1, flip=False, planar_hw=(h + 1, w + 1))
     # tiny images (<= 16^2 after the block): re-interleave (a [B,C,<=17,<=17] copy) and use the generic kernel, as the generator does
     return K._upfirdn2d_raw(K.unplanar(t, w // 2), _blur_kernel(t.device), h, w, 1, 1, 1, 1, flip=False)

@@ -159,6 +159,24 @@ def _upfirdn2d_raw(x, kernel, out_h, out_w, up, down, pad_x0, pad_y0, flip, act=
     return y
 
 
+_FirPlanFields = ctypes.c_int64 * 9  # W2E_FIR_PLAN_FIELDS
+
+
+def upfirdn_plan(planes, in_hw, out_hw, kernel_shape, up=1, down=1, pad_x0=0, planar=False, act=False, x_misalign=0, y_misalign=0):
+    """w2e_upfirdn2d_plan (include/w2e.h): [kernel, act, planar, grid, block, lds, arg0, arg1, arg2] of the launch w2e_upfirdn2d would
+    make -- kernel: 0 generic, 1 down4, 2 tile, 3 tile4, 4 blur4, 5 stream4 (W2E_FIR_*).  A launch it refuses raises its message."""
+    out = _FirPlanFields()
+    call("w2e_upfirdn2d_plan", planes, *in_hw, *out_hw, *kernel_shape, up, down, pad_x0, int(planar),
+         planar_pitch((in_hw[1] - 1) // 2) if planar else 0, int(act), x_misalign, y_misalign, out)
+    return out[:]
+
+
+def fir_planar_ok(kernel_shape, out_w):
+    """Whether w2e_upfirdn2d reads the UP conv's phase-planar image directly for an up = down = 1 FIR of these taps onto `out_w` columns
+    (w2e_upfirdn2d_planar_ok); where it does not, the caller re-interleaves the image first (unplanar)."""
+    return bool(_lib.load().w2e_upfirdn2d_planar_ok(kernel_shape[0], kernel_shape[1], 1, 1, out_w))
+
+
 class _UpFirDn2d(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, kernel, up, down, pad0, pad1):
@@ -384,6 +402,14 @@ def _upblur_planned(b, k, n, h, w):
     fp32 only, the layers it measured faster on)."""
     fused = ctypes.c_int(0)
     call("w2e_modconv_upblur_plan", b, k, n, h, w, ctypes.byref(fused))
+    return bool(fused.value)
+
+
+def _blur_actbwd_planned(planes, h, w, kernel_shape):
+    """Whether the library takes the activation backward + adjoint blur of a [planes,h,w] gradient as ONE pass
+    (w2e_blur_adjoint_actbwd_plan: the launcher's shape rules, not in deterministic mode, option tune_fuse)."""
+    fused = ctypes.c_int(0)
+    call("w2e_blur_adjoint_actbwd_plan", planes, h, w, kernel_shape[0], kernel_shape[1], ctypes.byref(fused))
     return bool(fused.value)
 
 
@@ -621,7 +647,7 @@ class _StyledConv(torch.autograd.Function):
             out = _modconv_upblur_raw(x, wp_f, s, d, blur_kernel, h, w, act)
         elif upsample:
             t, _ = _modconv_raw(MODE_UP, x, wp_f, s, d, h, w)
-            if w >= 16:   # the tile kernel reads the phase-planar layout directly
+            if fir_planar_ok(blur_kernel.shape, 2 * w):  # the tile kernel reads the phase-planar layout directly
                 out = _upfirdn2d_raw(t, blur_kernel, 2 * h, 2 * w, 1, 1, 1, 1, True,
                                      act=((None,) + act) if fuse_act else None, planar_hw=(2 * h + 1, 2 * w + 1))
             else:         # tiny images: re-interleave (a [B,C,<=17,<=17] copy) and use the generic kernel
@@ -663,8 +689,7 @@ class _StyledConv(torch.autograd.Function):
             gpre, sums = gout, pre_sums
         elif fuse_act:
             sums = torch.empty((b, cout, 3), device=x.device, dtype=torch.float32)
-            if (upsample and ow >= 256 and ow % 4 == 0 and tuple(blur_kernel.shape) == (4, 4) and not _lib.get_option("deterministic")
-                    and _lib.get_option("tune_fuse") != 0):  # (tune_fuse = 0: the two-kernel form, for comparison)
+            if upsample and _blur_actbwd_planned(b * cout, oh, ow, blur_kernel.shape):
                 # wide up-sampling layers: activation backward, its three reductions and the adjoint blur in ONE pass over
                 # (gout, out) -- the pre-activation gradient is never written (3 tensor passes instead of 5)
                 gpre = torch.empty((b, cout, oh + 1, ow + 1), device=x.device, dtype=torch.float32)
