@@ -54,7 +54,8 @@ extern "C" {
  * Still 7, additive: w2e_image_resize_plan / w2e_image_resize / w2e_image_quantize (w2e_image.h: Pillow-exact resize in,
  * torchvision-exact bytes out).
  * Still 7, additive: w2e_upfirdn2d_plan / w2e_upfirdn2d_planar_ok / w2e_blur_adjoint_actbwd_plan (the FIR dispatcher's decisions as
- * host-side queries). */
+ * host-side queries).
+ * Still 7, additive: w2e_jpeg_plan / w2e_jpeg_coefficients / w2e_jpeg_entropy (w2e_jpeg.h: Pillow's default JPEG, byte for byte). */
 #define W2E_VERSION 7
 
 int w2e_version(void);

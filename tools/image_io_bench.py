@@ -11,6 +11,13 @@ config-5 pipeline with bytes at both ends against floats at both ends.
   pipeline    capture_invert_and_edit at batch 8, float in / float out against uint8 in / uint8 out, each with the device-to-host
               copy of its images and mask into pinned memory
 
+  --jpeg      to_jpeg  uint8 [B,1024,1024,3] -> B files     vs  .cpu(), then Pillow's save per image on one host core
+              save_image  fp32 [B,3,1024,1024] -> one file  vs  to_bytes, .cpu(), Pillow's save   (B = 1, 4, 8: a row of B images;
+                                                                and B = 8 with nrow = 4: the 2 x 4 grid canvas)
+              both ends on the host, so these are host-clock times of whole calls (time_host); and the two stages of the encoder
+              alone (w2e_jpeg_coefficients, w2e_jpeg_entropy) on device events, with the bytes each moves.  Smooth-plus-noise
+              images, not noise.  Lines go to --jpeg-out (profiles/jpeg_bench.jsonl).
+
 HIP events around `--inner` back-to-back calls of the Python entry point, device-synchronised, after a warm-up; the variants of a
 group alternate, `--repeats` times each (>= 5): the median, with min .. max as the spread a difference has to exceed.  `bytes` is
 what the call has to move (input + output), GB/s = bytes / median.  One JSON line per (group, variant, batch), appended to --out.
@@ -167,12 +174,101 @@ def bench_pipeline(a, lines, batch=8):
                           d2h_bytes=d2h))
 
 
+def time_host(variants, repeats):
+    """{name: [ms per call]} on the host clock: every variant ends with its bytes on the host, so the call itself synchronises.  The
+    variants alternate; the device is drained before each interval."""
+    for fn in variants.values():
+        for _ in range(3):
+            fn()
+    times = {n: [] for n in variants}
+    for _ in range(repeats):
+        for name, fn in variants.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            times[name].append((time.perf_counter() - t0) * 1e3)
+    return times
+
+
+def photo_u8(b, h, w, seed):
+    """Smooth plus noise, uint8 [b,h,w,3]: the statistics of a generated face more than those of noise (which no JPEG compresses)."""
+    g = torch.Generator().manual_seed(seed)
+    yy, xx = torch.meshgrid(torch.arange(h) / h, torch.arange(w) / w, indexing="ij")
+    base = torch.stack([128 + 100 * torch.sin(6 * xx + 2 * yy), 128 + 100 * torch.cos(5 * yy - xx), 128 + 90 * torch.sin(9 * xx * yy)], -1)
+    return (base[None] + 6 * torch.randn(b, h, w, 3, generator=g)).clamp_(0, 255).to(torch.uint8)
+
+
+def bench_jpeg(a, lines):
+    """to_jpeg / save_image against what a caller does today (the canvas to the host, Pillow's encoder on one host core), and the two
+    stages of the encoder alone.  Host-clock times for the calls that end on the host, device events for the stages."""
+    import io
+    from where2edit_amd import image_io as I
+    from where2edit_amd._lib import call, stream_ptr
+    try:
+        from PIL import Image
+    except ImportError:
+        Image = None
+    dev = "cuda"
+
+    def pillow(canvas_host):
+        buf = io.BytesIO()
+        Image.fromarray(canvas_host.numpy()).save(buf, format="JPEG")
+        return buf.getvalue()
+
+    for b in (1, 4, 8):
+        u8 = photo_u8(b, 1024, 1024, b).to(dev)
+        files = I.to_jpeg(u8)
+        coded = sum(len(f) for f in files)
+        variants = {"hip": lambda: I.to_jpeg(u8)}
+        extra = {"coded_bytes": coded}
+        if Image is not None:
+            variants["d2h_then_pillow"] = lambda: [pillow(img) for img in u8.cpu()]
+            extra["equal_to_pillow"] = files == [pillow(img) for img in u8.cpu()]
+        t = time_host(variants, a.repeats)
+        for name, ms in t.items():
+            lines.append(line("to_jpeg_1024", name, b, ms, u8.numel() + coded, **extra))
+        # the stages alone
+        plan = I.jpeg_plan(b, 1024, 1024)
+        coef = torch.empty((b, plan["blocks"], 64), dtype=torch.int16, device=dev)
+        out = torch.empty((b, plan["segment"]), dtype=torch.uint8, device=dev)
+        lengths = torch.empty((b,), dtype=torch.int64, device=dev)
+        work = torch.empty((plan["workspace"],), dtype=torch.uint8, device=dev)
+        huff = I._huff_table(torch.device(dev, torch.cuda.current_device()))
+        stage1 = lambda: call("w2e_jpeg_coefficients", I._p(u8), b, 1024, 1024, 75, I._p(coef), stream_ptr())
+        stage2 = lambda: call("w2e_jpeg_entropy", I._p(coef), b, 1024, 1024, I._p(huff), I._p(out), plan["segment"], I._p(lengths), I._p(work), stream_ptr())
+        stage1()
+        t = time_group({"coefficients": stage1, "entropy": stage2}, a.repeats, a.inner)
+        seg = int(lengths.sum())
+        lines.append(line("jpeg_stage_1024", "coefficients", b, t["coefficients"], u8.numel() + coef.numel() * 2))
+        # entropy: coefficients in, slot words and lengths out and in again, offsets out and in, the segment out
+        lines.append(line("jpeg_stage_1024", "entropy", b, t["entropy"], coef.numel() * 2 + 2 * (seg + 4 * b * plan["blocks"]) + 16 * b * plan["blocks"] + seg,
+                          segment_bytes=seg))
+        del coef, out, work
+        x = (u8.permute(0, 3, 1, 2).float() / 127.5 - 1).contiguous()
+        for nrow, group in ((8, "save_image_1024"),) + (((4, "save_image_1024_grid_2x4"),) if b == 8 else ()):
+            def ours():
+                buf = io.BytesIO()
+                I.save_image(x, buf, nrow=nrow)
+                return buf.getvalue()
+            variants = {"hip": ours}
+            extra = {"coded_bytes": len(ours()), "canvas": list(I.grid_shape(b, 1024, 1024, nrow))}
+            if Image is not None:
+                variants["to_bytes_d2h_then_pillow"] = lambda: pillow(I.to_bytes(x, nrow=nrow).cpu())
+                extra["equal_to_pillow"] = ours() == variants["to_bytes_d2h_then_pillow"]()
+            t = time_host(variants, a.repeats)
+            for name, ms in t.items():
+                lines.append(line(group, name, b, ms, x.numel() * 4 + extra["coded_bytes"], **extra))
+        del x, u8
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--inner", type=int, default=10)
     ap.add_argument("--skip-pipeline", action="store_true")
+    ap.add_argument("--jpeg", action="store_true", help="only the JPEG calls; lines go to --jpeg-out")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "image_io_bench.jsonl"))
+    ap.add_argument("--jpeg-out", default=os.path.join(ROOT, "profiles", "jpeg_bench.jsonl"))
     a = ap.parse_args()
     if a.repeats < 5:
         raise SystemExit("--repeats must be >= 5: the spread is part of the result")
@@ -180,14 +276,18 @@ def main():
         raise SystemExit("image_io_bench needs the GPU: a host timing says nothing about these kernels")
     lines = []
     with torch.no_grad():
-        bench_calls(a, lines)
-        if not a.skip_pipeline:
-            bench_pipeline(a, lines)
+        if a.jpeg:
+            bench_jpeg(a, lines)
+        else:
+            bench_calls(a, lines)
+            if not a.skip_pipeline:
+                bench_pipeline(a, lines)
     for ln in lines:
         print(json.dumps(ln))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "a") as f:
+    out = a.jpeg_out if a.jpeg else a.out
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "a") as f:
             for ln in lines:
                 f.write(json.dumps(ln) + "\n")
 

@@ -60,7 +60,8 @@ def r1_penalty(discriminator, real, return_logits=False):
 
 # where2edit_amd.evaluation's public names, importable from the package (resolved on first use: importing the package stays light)
 _EVALUATION = ("CELEBAMASK_REGIONS", "region_lut", "binarise", "attention_with_text", "MaskIoU", "calculate_iou")
-_IMAGE_IO = ("resample_tables", "resize_u8", "to_tensor", "label_ids", "to_bytes")
+_IMAGE_IO = ("resample_tables", "resize_u8", "to_tensor", "label_ids", "to_bytes", "jpeg_tables", "jpeg_header", "jpeg_coefficients", "to_jpeg",
+             "save_image")
 
 
 def __getattr__(name):

@@ -88,6 +88,10 @@ _PROTOS = {
     "w2e_image_resize_plan": (_I, [_I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int64)]),
     "w2e_image_resize": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P]),
     "w2e_image_quantize": (_I, [_P, _I, _I, _I, _I, _F, _F, _F, _I, _I, _F, _I, _P, _P]),
+    # include/w2e_jpeg.h (image_io.py)
+    "w2e_jpeg_plan": (_I, [_I, _I, _I, ctypes.POINTER(ctypes.c_int64)]),
+    "w2e_jpeg_coefficients": (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    "w2e_jpeg_entropy": (_I, [_P, _I, _I, _I, _P, _P, _L, _P, _P, _P]),
 }
 
 _lib = None

@@ -23,6 +23,16 @@ __device__ __forceinline__ unsigned wave_sum(unsigned v) {
     for (int off = 32; off > 0; off >>= 1) v += (unsigned)__shfl_xor((int)v, off, 64);
     return v;
 }
+// inclusive prefix sum over the 64 lanes (lane 63 ends with the wave's sum): six shift-and-add steps
+__device__ __forceinline__ unsigned wave_scan_inclusive(unsigned v) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned t = (unsigned)__shfl_up((int)v, off, 64);
+        if (lane >= off) v += t;
+    }
+    return v;
+}
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));

@@ -11,11 +11,18 @@ Out.  Every path of the reference that emits an image ends in `torchvision.utils
 (mapper/scripts/inference.py:70-77, utils.py:493-503, coach.py:264).  `to_bytes` is that call up to the bytes it hands to the PNG
 encoder: torchvision 0.8.2's make_grid normalisation and layout, then mul(255).add_(0.5).clamp_(0, 255).to(uint8), as one kernel.
 
-Decoding and encoding (JPEG, PNG) stay with the caller.  GPU only: there is no CPU fallback (tests/imageio_ref.py is the numpy
-restatement the kernels are tested against)."""
+Every file the reference writes is a `.jpg`: torchvision ends `save_image` in `Image.fromarray(ndarr).save(fp)`, Pillow's default JPEG
+(libjpeg: quality 75, 4:2:0, the Annex K Huffman tables, no optimisation).  `to_jpeg` is that encoder on the device, in integers from
+end to end, so the file is Pillow's byte for byte (include/w2e_jpeg.h, csrc/jpeg.hip; DESIGN.md "K17b"): colour conversion,
+down-sampling, DCT, quantisation and Huffman coding are kernels; the header, byte stuffing and the end marker are host work on the
+coded segment, which is what crosses to the host (a few per cent of the pixels).  `save_image` is `to_bytes` + `to_jpeg` + the file.
+
+Decoding, and PNG encoding, stay with the caller.  GPU only: there is no CPU fallback (tests/imageio_ref.py and tests/jpeg_ref.py are
+the numpy restatements the kernels are tested against)."""
 import ctypes
 import functools
 import math
+import os
 
 import torch
 
@@ -251,6 +258,176 @@ def to_bytes(x, value_range=(-1, 1), nrow=8, padding=2, pad_value=0.0, grid=True
     return out
 
 
+# ---- JPEG (include/w2e_jpeg.h) ----
+# Annex K of the JPEG standard: the quantisation base tables in natural order, and the four Huffman tables as (class << 4 | id,
+# codes per length 1..16, symbols in code order), in the order the header writes them and the device table holds them.
+_JPEG_LUMA_Q = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+                18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99)
+_JPEG_CHROMA_Q = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32
+_JPEG_AC_LUMA = bytes.fromhex(
+    "01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738393a434445464748494a"
+    "535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7"
+    "c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa")
+_JPEG_AC_CHROMA = bytes.fromhex(
+    "000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a35363738393a434445464748494a"
+    "535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6"
+    "c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa")
+_JPEG_HUFFMAN = (
+    (0x00, (0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0), bytes(range(12))),
+    (0x10, (0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7D), _JPEG_AC_LUMA),
+    (0x01, (0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0), bytes(range(12))),
+    (0x11, (0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77), _JPEG_AC_CHROMA),
+)
+# _JPEG_ZIGZAG[k]: the natural (row-major) index of the k-th coefficient of the zigzag scan
+_JPEG_ZIGZAG = tuple(sorted(range(64), key=lambda i: (i // 8 + i % 8, i // 8 if (i // 8 + i % 8) % 2 else i % 8)))
+_JPEG_GUESS_DIVISOR = 2  # to_jpeg's first copy takes h * w / 2 bytes per image: 4 bits per pixel, several times a photograph's rate
+_HUFF_TABLES = {}        # device -> uint32 [4, 256]
+
+
+def _check_quality(who, quality):
+    if not (isinstance(quality, int) and not isinstance(quality, bool) and 1 <= quality <= 100):
+        raise ValueError(f"{who}: quality is an integer in 1..100 (got {quality!r})")
+
+
+@functools.lru_cache(maxsize=None)
+def _jpeg_tables(quality):
+    scale = 5000 // quality if quality < 50 else 200 - 2 * quality
+    return tuple(torch.tensor([min(max((v * scale + 50) // 100, 1), 255) for v in base], dtype=torch.int32) for base in (_JPEG_LUMA_Q, _JPEG_CHROMA_Q))
+
+
+def jpeg_tables(quality=75):
+    """The two quantisation tables of a quality in 1..100: int32 CPU tensors (luminance [64], chrominance [64]) in natural (row-major)
+    order.  The Annex K base tables scaled as libjpeg's jpeg_set_quality does with baseline forced: scale = 5000 // q below 50,
+    200 - 2 q from there; entry = clamp((base * scale + 50) // 100, 1, 255).  The result is cached: treat it as read-only."""
+    _check_quality("jpeg_tables", quality)
+    return _jpeg_tables(quality)
+
+
+def _jpeg_segment(marker, payload):
+    return bytes((0xFF, marker)) + (len(payload) + 2).to_bytes(2, "big") + payload
+
+
+def jpeg_header(h, w, quality=75):
+    """The bytes of the file from SOI through SOS, as Pillow writes them for an h x w RGB image: APP0 (JFIF 1.1, density 1 x 1, no
+    unit), one DQT per table (8-bit, zigzag order), SOF0 (Y 2x2 on table 0, Cb and Cr 1x1 on table 1), four DHT (DC0, AC0, DC1, AC1: the
+    Annex K tables), SOS."""
+    _check_size("jpeg_header", h), _check_size("jpeg_header", w)
+    luma, chroma = (t.tolist() for t in jpeg_tables(quality))
+    out = b"\xff\xd8" + _jpeg_segment(0xE0, b"JFIF\0" + bytes((1, 1, 0, 0, 1, 0, 1, 0, 0)))
+    out += _jpeg_segment(0xDB, bytes([0] + [luma[i] for i in _JPEG_ZIGZAG])) + _jpeg_segment(0xDB, bytes([1] + [chroma[i] for i in _JPEG_ZIGZAG]))
+    out += _jpeg_segment(0xC0, bytes([8]) + h.to_bytes(2, "big") + w.to_bytes(2, "big") + bytes((3, 1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1)))
+    for ident, counts, symbols in _JPEG_HUFFMAN:
+        out += _jpeg_segment(0xC4, bytes([ident]) + bytes(counts) + symbols)
+    return out + _jpeg_segment(0xDA, bytes((3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0)))
+
+
+def jpeg_code_table():
+    """The device's view of the four Huffman tables: uint32 CPU [4, 256] in the order DC0, AC0, DC1, AC1, entry [symbol] =
+    (code << 5) | length, 0 for a symbol the table does not have.  Codes are assigned as Annex C says: in order of length, counting
+    up, shifted left at each new length."""
+    table = torch.zeros((4, 256), dtype=torch.int64)
+    for t, (_, counts, symbols) in enumerate(_JPEG_HUFFMAN):
+        code, k = 0, 0
+        for length in range(1, 17):
+            for _ in range(counts[length - 1]):
+                table[t, symbols[k]] = (code << 5) | length
+                code, k = code + 1, k + 1
+            code <<= 1
+    return table.to(torch.int32)  # (every entry is below 2^21)
+
+
+def _huff_table(device):
+    hit = _HUFF_TABLES.get(device)
+    if hit is None:
+        hit = _HUFF_TABLES[device] = jpeg_code_table().to(device)
+    return hit
+
+
+def jpeg_plan(batch, h, w):
+    """w2e_jpeg_plan as a dict: blocks per image, the MCU grid, the entropy stage's workspace bytes, the largest possible segment of
+    an image in bytes, the coefficient elements per image, stage 1's workgroups and the prefix sum's tile.  Pure host."""
+    plan = (ctypes.c_int64 * 8)()
+    call("w2e_jpeg_plan", batch, h, w, plan)
+    return {"blocks": plan[0], "mcus": (plan[2], plan[1]), "workspace": plan[3], "segment": plan[4], "coefficients": plan[5],
+            "strips": plan[6], "scan_tile": plan[7]}
+
+
+def _jpeg_input(who, x, quality):
+    _on_gpu(who, "x", x, torch.uint8, (3, 4))
+    if x.shape[-1] != 3:
+        raise RuntimeError(f"{who}: images are [H,W,3] or [B,H,W,3], RGB, channels last (got shape {tuple(x.shape)})")
+    _check_quality(who, quality)
+    x4 = x.unsqueeze(0) if x.ndim == 3 else x
+    _check_size(who, x4.shape[1]), _check_size(who, x4.shape[2])
+    return x4 if x4.is_contiguous() else x4.contiguous()
+
+
+def _jpeg_coefficients(x4, quality, plan):
+    b, h, w, _ = x4.shape
+    coef = torch.empty((b, plan["blocks"], 64), dtype=torch.int16, device=x4.device)
+    call("w2e_jpeg_coefficients", _p(x4), b, h, w, quality, _p(coef), stream_ptr())
+    return coef
+
+
+def jpeg_coefficients(x, quality=75):
+    """Stage 1 of the encoder on its own (for tests and for finding a fault): uint8 [H,W,3] or [B,H,W,3] on the GPU -> int16
+    [blocks, 64] or [B, blocks, 64], the quantised DCT coefficients of every block in zigzag order.  Blocks are in scan order: MCUs
+    of 16 x 16 pixels in raster order, Y(0,0) Y(0,1) Y(1,0) Y(1,1) Cb Cr inside each; a Y block outside the image (a dummy) has zero
+    AC coefficients and the DC of the block before it."""
+    x4 = _jpeg_input("jpeg_coefficients", x, quality)
+    with torch.cuda.device(x4.device):
+        coef = _jpeg_coefficients(x4, quality, jpeg_plan(*x4.shape[:3]))
+    return coef[0] if x.ndim == 3 else coef
+
+
+def to_jpeg(x, quality=75):
+    """`Image.fromarray(x).save(fp, format="JPEG", quality=quality)` of images on the GPU, byte for byte: uint8 [H,W,3] -> bytes,
+    uint8 [B,H,W,3] -> a list of B bytes.  Four launches for the whole batch; what crosses to the host is the coded data, not the
+    pixels, in ONE copy (lengths included) as long as no image codes to more than 4 bits per pixel -- several times the rate of a
+    photograph at quality 75; past that (noise at a high quality) a second copy fetches the rest."""
+    x4 = _jpeg_input("to_jpeg", x, quality)
+    b, h, w, _ = x4.shape
+    if b == 0:
+        return []
+    with torch.cuda.device(x4.device):
+        dev = x4.device
+        plan = jpeg_plan(b, h, w)
+        coef = _jpeg_coefficients(x4, quality, plan)
+        cap = plan["segment"]
+        out = torch.empty((b, cap), dtype=torch.uint8, device=dev)
+        lengths = torch.empty((b,), dtype=torch.int64, device=dev)
+        work = torch.empty((plan["workspace"],), dtype=torch.uint8, device=dev)
+        call("w2e_jpeg_entropy", _p(coef), b, h, w, _p(_huff_table(dev)), _p(out), cap, _p(lengths), _p(work), stream_ptr())
+        guess = min(cap, h * w // _JPEG_GUESS_DIVISOR + 1024)
+        packed = torch.cat((lengths.view(torch.uint8).view(b, 8), out[:, :guess]), dim=1).cpu().numpy()
+        sizes = packed[:, :8].copy().view("<i8").ravel().tolist()
+        data = packed[:, 8:]
+        if max(sizes) > guess:
+            data = out[:, :max(sizes)].cpu().numpy()
+    head = jpeg_header(h, w, quality)
+    files = [head + data[i, :n].tobytes().replace(b"\xff", b"\xff\x00") + b"\xff\xd9" for i, n in enumerate(sizes)]
+    return files[0] if x.ndim == 3 else files
+
+
+def save_image(x, fp, nrow=8, padding=2, value_range=(-1, 1), pad_value=0.0, quality=75):
+    """`torchvision.utils.save_image(x, fp, nrow=, padding=, normalize=True, range=value_range, pad_value=)` (0.8.2) for a `.jpg`:
+    fp32 [B,C,H,W] (C = 1 or 3) on the GPU -> to_bytes' canvas -> to_jpeg -> the file.  fp: a path ending in .jpg / .jpeg, or an
+    object with write() (the reference only ever writes JPEG; PNG is not implemented)."""
+    if isinstance(fp, (str, os.PathLike)):
+        if os.path.splitext(os.fspath(fp))[1].lower() not in (".jpg", ".jpeg"):
+            raise ValueError(f"save_image: {os.fspath(fp)!r} does not end in .jpg or .jpeg; PNG (and every other format) is not implemented")
+    elif not hasattr(fp, "write"):
+        raise ValueError(f"save_image: fp is a path ending in .jpg / .jpeg or an object with write() (got {type(fp).__name__})")
+    _check_quality("save_image", quality)
+    data = to_jpeg(to_bytes(x, value_range=value_range, nrow=nrow, padding=padding, pad_value=pad_value, grid=True), quality)
+    if hasattr(fp, "write"):
+        fp.write(data)
+    else:
+        with open(fp, "wb") as f:
+            f.write(data)
+
+
 def clear_caches():
-    """Drop the device copies of the coefficient and normalisation tables (they are small; this is for tests and device resets)."""
-    _DEVICE_TABLES.clear(), _NORM_TABLES.clear()
+    """Drop the device copies of the coefficient, normalisation and Huffman tables (they are small; this is for tests and device
+    resets)."""
+    _DEVICE_TABLES.clear(), _NORM_TABLES.clear(), _HUFF_TABLES.clear()
