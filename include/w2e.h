@@ -55,7 +55,9 @@ extern "C" {
  * torchvision-exact bytes out).
  * Still 7, additive: w2e_upfirdn2d_plan / w2e_upfirdn2d_planar_ok / w2e_blur_adjoint_actbwd_plan (the FIR dispatcher's decisions as
  * host-side queries).
- * Still 7, additive: w2e_jpeg_plan / w2e_jpeg_coefficients / w2e_jpeg_entropy (w2e_jpeg.h: Pillow's default JPEG, byte for byte). */
+ * Still 7, additive: w2e_jpeg_plan / w2e_jpeg_coefficients / w2e_jpeg_entropy (w2e_jpeg.h: Pillow's default JPEG, byte for byte).
+ * Still 7, additive: w2e_jpeg_decode_plan / w2e_jpeg_decode_sync / w2e_jpeg_decode_coefficients / w2e_jpeg_pixels (w2e_jpeg.h: baseline
+ * JPEG decoding, Pillow's pixels). */
 #define W2E_VERSION 7
 
 int w2e_version(void);

@@ -18,6 +18,11 @@ config-5 pipeline with bytes at both ends against floats at both ends.
               alone (w2e_jpeg_coefficients, w2e_jpeg_entropy) on device events, with the bytes each moves.  Smooth-plus-noise
               images, not noise.  Lines go to --jpeg-out (profiles/jpeg_bench.jsonl).
 
+  --decode    from_jpeg  B files -> uint8 [B,1024,1024,3]   vs  Pillow's decoder per file on one host core, then .to("cuda")
+              (the photograph of tests/jpeg_ref.py at quality 75 and 95, B = 1 and 8, sub_bits 256 / 512 / 1024; the constant image:
+              the relaxation's worst case) on the host clock, with the number of launches; and the stages alone.  Lines go to
+              --decode-out (profiles/jpeg_decode_bench.jsonl).
+
 HIP events around `--inner` back-to-back calls of the Python entry point, device-synchronised, after a warm-up; the variants of a
 group alternate, `--repeats` times each (>= 5): the median, with min .. max as the spread a difference has to exceed.  `bytes` is
 what the call has to move (input + output), GB/s = bytes / median.  One JSON line per (group, variant, batch), appended to --out.
@@ -261,6 +266,69 @@ def bench_jpeg(a, lines):
         del x, u8
 
 
+def bench_decode(a, lines):
+    """from_jpeg against what a caller does today (Pillow's decoder on one host core, then the pixels to the device), for the
+    1024 x 1024 photograph of tests/jpeg_ref.py at quality 75 and 95, batches of 1 and 8, subsequences of 256 / 512 / 1024 bits; the
+    constant image, whose relaxation takes as many rounds as it has subsequences; and the stages alone.  Host-clock times of whole
+    calls (both end synchronised), device events for the stages that do not synchronise."""
+    import io
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import jpeg_ref as R
+    from where2edit_amd import image_io as I
+    try:
+        from PIL import Image
+    except ImportError:
+        Image = None
+    dev = torch.device("cuda", torch.cuda.current_device())
+    subs = (256, 512, 1024)
+
+    def pillow(files):
+        out = torch.from_numpy(np.stack([np.asarray(Image.open(io.BytesIO(f)).convert("RGB")) for f in files])).to(dev)
+        torch.cuda.synchronize()
+        return out
+
+    for quality in (75, 95):
+        for b in (1, 8):
+            files = I.to_jpeg(torch.from_numpy(np.stack([R.photo(1024, 1024, seed) for seed in range(b)])).to(dev), quality)
+            coded = sum(len(f) for f in files)
+            variants = {f"hip_sub{sb}": (lambda sb=sb: I.from_jpeg(files, sub_bits=sb, stack=True)) for sb in subs}
+            extra = {"quality": quality, "coded_bytes": coded}
+            if Image is not None:
+                variants["pillow_then_h2d"] = lambda: pillow(files)
+                extra["equal_to_pillow"] = all(torch.equal(fn(), pillow(files)) for name, fn in variants.items() if name.startswith("hip"))
+            t = time_host(variants, a.repeats)
+            for name, ms in t.items():
+                launches = I.jpeg_decode_states(files, int(name[7:]))[1] if name.startswith("hip") else None
+                lines.append(line("from_jpeg_1024", name, b, ms, coded + b * 1024 * 1024 * 3, launches=launches, **extra))
+            # the stages alone
+            parsed = [I.jpeg_parse(f) for f in files]
+            for sb in subs:
+                batch = I._JpegBatch(parsed, dev, sb)
+                t = time_host({"relax": batch.relax}, a.repeats)
+                lines.append(line("jpeg_decode_stage_1024", f"relax_sub{sb}", b, t["relax"], coded, launches=batch.relax(), quality=quality,
+                                  subsequences=batch.plan["subsequences"]))
+                coef, status = batch.coefficients()
+                quant = batch.quant.to(dev)
+                t = time_group({"coefficients": batch.coefficients, "pixels": lambda: I._jpeg_pixels(coef, quant, 1024, 1024, batch.sampling, batch.plan)},
+                               a.repeats, a.inner)
+                lines.append(line("jpeg_decode_stage_1024", f"coefficients_sub{sb}", b, t["coefficients"], 2 * coded + coef.numel() * 2, quality=quality))
+                if sb == subs[-1]:
+                    lines.append(line("jpeg_decode_stage_1024", "pixels", b, t["pixels"], coef.numel() * 2 + 2 * b * 1024 * 1024 * 3 // 2 + b * 1024 * 1024 * 3,
+                                      quality=quality))
+                del batch, coef
+    # the worst case of the relaxation: every MCU of a constant image codes alike, so a wrong phase never meets the right one
+    flat = I.to_jpeg(torch.from_numpy(R.pattern("constant", 1024, 1024)).to(dev))
+    variants = {f"hip_sub{sb}": (lambda sb=sb: I.from_jpeg(flat, sub_bits=sb)) for sb in subs}
+    if Image is not None:
+        variants["pillow_then_h2d"] = lambda: pillow([flat])
+    t = time_host(variants, a.repeats)
+    for name, ms in t.items():
+        states, launches = I.jpeg_decode_states(flat, int(name[7:])) if name.startswith("hip") else (None, None)
+        lines.append(line("from_jpeg_1024_constant", name, 1, ms, len(flat) + 1024 * 1024 * 3, launches=launches, coded_bytes=len(flat),
+                          subsequences=None if states is None else int(states.shape[0])))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=20)
@@ -269,6 +337,8 @@ def main():
     ap.add_argument("--jpeg", action="store_true", help="only the JPEG calls; lines go to --jpeg-out")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "image_io_bench.jsonl"))
     ap.add_argument("--jpeg-out", default=os.path.join(ROOT, "profiles", "jpeg_bench.jsonl"))
+    ap.add_argument("--decode", action="store_true", help="only the JPEG decoder; lines go to --decode-out")
+    ap.add_argument("--decode-out", default=os.path.join(ROOT, "profiles", "jpeg_decode_bench.jsonl"))
     a = ap.parse_args()
     if a.repeats < 5:
         raise SystemExit("--repeats must be >= 5: the spread is part of the result")
@@ -278,13 +348,15 @@ def main():
     with torch.no_grad():
         if a.jpeg:
             bench_jpeg(a, lines)
+        elif a.decode:
+            bench_decode(a, lines)
         else:
             bench_calls(a, lines)
             if not a.skip_pipeline:
                 bench_pipeline(a, lines)
     for ln in lines:
         print(json.dumps(ln))
-    out = a.jpeg_out if a.jpeg else a.out
+    out = a.jpeg_out if a.jpeg else (a.decode_out if a.decode else a.out)
     if out:
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
         with open(out, "a") as f:

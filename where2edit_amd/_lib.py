@@ -92,6 +92,10 @@ _PROTOS = {
     "w2e_jpeg_plan": (_I, [_I, _I, _I, ctypes.POINTER(ctypes.c_int64)]),
     "w2e_jpeg_coefficients": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "w2e_jpeg_entropy": (_I, [_P, _I, _I, _I, _P, _P, _L, _P, _P, _P]),
+    "w2e_jpeg_decode_plan": (_I, [_I, _I, _I, _I, _L, _I, ctypes.POINTER(ctypes.c_int64)]),
+    "w2e_jpeg_decode_sync": (_I, [_P, _P, _P, _L, _I, _I, _I, _I, _L, _I, _I, _P, _P, _P]),
+    "w2e_jpeg_decode_coefficients": (_I, [_P, _P, _P, _L, _I, _I, _I, _I, _L, _I, _P, _P, _P, _P]),
+    "w2e_jpeg_pixels": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
 }
 
 _lib = None

@@ -17,13 +17,20 @@ end to end, so the file is Pillow's byte for byte (include/w2e_jpeg.h, csrc/jpeg
 down-sampling, DCT, quantisation and Huffman coding are kernels; the header, byte stuffing and the end marker are host work on the
 coded segment, which is what crosses to the host (a few per cent of the pixels).  `save_image` is `to_bytes` + `to_jpeg` + the file.
 
-Decoding, and PNG encoding, stay with the caller.  GPU only: there is no CPU fallback (tests/imageio_ref.py and tests/jpeg_ref.py are
-the numpy restatements the kernels are tested against)."""
+Files in.  Every real-image path of the reference starts with `Image.open(path)` on a JPEG (show_demo/try_demo.py:96-99; the
+CelebAMask-HQ images, utils.py:573-587).  `from_jpeg` / `load_image` decode a baseline file on the device to Pillow's own pixels
+(csrc/jpeg_decode.hip; DESIGN.md "K17c"): the host walks the markers (`jpeg_parse`), only the coded file crosses to the device, the
+Huffman stream is decoded in parallel by self-synchronisation, then inverse DCT, chroma up-sampling and colour conversion.
+
+PNG stays with the caller.  GPU only: there is no CPU fallback (tests/imageio_ref.py, tests/jpeg_ref.py and tests/jpeg_decode_ref.py
+are the numpy restatements the kernels are tested against)."""
 import ctypes
 import functools
 import math
 import os
+import re
 
+import numpy as np
 import torch
 
 from ._lib import call, stream_ptr
@@ -280,6 +287,7 @@ _JPEG_HUFFMAN = (
 )
 # _JPEG_ZIGZAG[k]: the natural (row-major) index of the k-th coefficient of the zigzag scan
 _JPEG_ZIGZAG = tuple(sorted(range(64), key=lambda i: (i // 8 + i % 8, i // 8 if (i // 8 + i % 8) % 2 else i % 8)))
+_JPEG_ZIGZAG_POS = tuple(_JPEG_ZIGZAG.index(i) for i in range(64))  # the inverse: the zigzag position of natural index i
 _JPEG_GUESS_DIVISOR = 2  # to_jpeg's first copy takes h * w / 2 bytes per image: 4 bits per pixel, several times a photograph's rate
 _HUFF_TABLES = {}        # device -> uint32 [4, 256]
 
@@ -425,6 +433,391 @@ def save_image(x, fp, nrow=8, padding=2, value_range=(-1, 1), pad_value=0.0, qua
     else:
         with open(fp, "wb") as f:
             f.write(data)
+
+
+# ---- JPEG decoding (include/w2e_jpeg.h, csrc/jpeg_decode.hip; DESIGN.md "K17c") ----
+JPEG_SAMPLINGS = ("420", "444", "grey")   # W2E_JPEG_420, W2E_JPEG_444, W2E_JPEG_GREY
+JPEG_SUB_BITS = 512                       # the default subsequence length of the entropy decoder, in bits: the fastest of 256 / 512 / 1024 at batch 8
+_JPEG_TABLE_WORDS = 384                   # W2E_JPEG_TABLE_WORDS
+_JPEG_MAX_SCAN_BITS = 0x7fff0000          # W2E_JPEG_MAX_SCAN_BITS
+_JPEG_SOF_NAMES = {0xC1: "an extended-sequential JPEG", 0xC2: "a progressive JPEG", 0xC3: "a lossless JPEG", 0xC5: "a hierarchical JPEG",
+                   0xC6: "a hierarchical JPEG", 0xC7: "a hierarchical JPEG", 0xC9: "an arithmetic-coded JPEG", 0xCA: "an arithmetic-coded JPEG",
+                   0xCB: "an arithmetic-coded JPEG", 0xCD: "an arithmetic-coded JPEG", 0xCE: "an arithmetic-coded JPEG", 0xCF: "an arithmetic-coded JPEG"}
+_JPEG_STATUS = ((1, "the scan does not hold the image's number of blocks"), (2, "a coefficient category above 11 (DC) or 10 (AC)"),
+                (4, "the scan ends inside a block"))
+_JPEG_NEXT_MARKER = re.compile(rb"\xff[^\x00]")
+
+
+def _refuse(what):
+    raise ValueError(f"jpeg_parse: the file is {what}, which the GPU decoder does not take; decode it with Pillow")
+
+
+def jpeg_parse(data):
+    """The host side of the decoder: walk the markers of a JPEG file and hand back what the kernels need, as a dict -- `h`, `w`,
+    `sampling` ("420" | "444" | "grey"), `tables` (int32 CPU [components, 64]: each component's quantisation table in natural,
+    row-major order), `huffman` (per component ((counts per length 1..16, symbols) of its DC table, the same of its AC table): the
+    file's own DHT lists) and `scan` (the entropy-coded segment up to EOI, byte stuffing 0xFF 0x00 -> 0xFF removed).
+    In scope: baseline sequential (SOF0), 8 bits, Huffman coded, one scan, no restart interval; one component (grey), or three that
+    are YCbCr by libjpeg's rule (a JFIF marker; otherwise an Adobe marker with transform 1; otherwise anything but the ids R, G, B)
+    sampled 4:4:4 or 4:2:0; sizes 1..16384.  Everything else -- progressive, 12 bits, arithmetic coding, DRI != 0, 4:2:2 and other
+    samplings, CMYK and RGB-coded files, several scans, data that is no JPEG -- raises a ValueError that names what the file is.  EXIF
+    orientation is ignored, as Image.open ignores it.  A file that ends inside its scan is NOT refused here: its scan goes to the
+    kernels as it is and their status refuses it."""
+    if isinstance(data, (bytearray, memoryview)):
+        data = bytes(data)
+    if not isinstance(data, bytes):
+        raise ValueError(f"jpeg_parse: data is the bytes of a JPEG file (got {type(data).__name__})")
+    if data[:8] == b"\x89PNG\r\n\x1a\n":
+        _refuse("a PNG")
+    if data[:2] != b"\xff\xd8":
+        _refuse("no JPEG (it does not begin with the SOI marker)")
+    at, quant, huff, frame, jfif, adobe = 2, {}, {}, None, False, None
+    cut = "a JPEG cut inside its header"
+    while True:
+        if at + 2 > len(data):
+            _refuse(cut)
+        if data[at] != 0xFF:
+            _refuse(f"a corrupt JPEG (no marker at byte {at})")
+        marker = data[at + 1]
+        if marker == 0xFF:  # a fill byte
+            at += 1
+            continue
+        if marker == 0xD9:
+            _refuse("a JPEG without a scan")
+        if at + 4 > len(data):
+            _refuse(cut)
+        size = int.from_bytes(data[at + 2:at + 4], "big")
+        if size < 2 or at + 2 + size > len(data):
+            _refuse(cut)
+        body = data[at + 4:at + 2 + size]
+        at += 2 + size
+        if marker == 0xE0 and body[:5] == b"JFIF\0":
+            jfif = True
+        elif marker == 0xEE and body[:5] == b"Adobe" and len(body) >= 12:
+            adobe = body[11]
+        elif marker == 0xDB:
+            while body:
+                if body[0] >> 4:
+                    _refuse("a JPEG with 16-bit quantisation tables")
+                if len(body) < 65 or (body[0] & 15) > 3:
+                    _refuse("a corrupt JPEG (a bad DQT segment)")
+                quant[body[0] & 15] = [body[1 + _JPEG_ZIGZAG_POS[i]] for i in range(64)]
+                body = body[65:]
+        elif marker == 0xC4:
+            while body:
+                counts = tuple(body[1:17])
+                if len(body) < 17 or (body[0] >> 4) > 1 or (body[0] & 15) > 3 or sum(counts) > 256 or len(body) < 17 + sum(counts):
+                    _refuse("a corrupt JPEG (a bad DHT segment)")
+                room = 1  # codes still free at the current length
+                for n in counts:
+                    room = 2 * room - n
+                    if room < 0:
+                        _refuse("a corrupt JPEG (a DHT segment whose codes do not fit their lengths)")
+                huff[body[0]] = (counts, bytes(body[17:17 + sum(counts)]))
+                body = body[17 + sum(counts):]
+        elif marker == 0xC0:
+            if frame is not None:
+                _refuse("a JPEG with several frames")
+            if len(body) < 6 or len(body) < 6 + 3 * body[5]:
+                _refuse(cut)
+            if body[0] != 8:
+                _refuse(f"a {body[0]}-bit JPEG")
+            h, w = int.from_bytes(body[1:3], "big"), int.from_bytes(body[3:5], "big")
+            frame = [(body[6 + 3 * i], body[7 + 3 * i], body[8 + 3 * i]) for i in range(body[5])]
+        elif marker in _JPEG_SOF_NAMES:
+            _refuse(_JPEG_SOF_NAMES[marker] + (f" ({body[0]} bits)" if body and body[0] != 8 else ""))
+        elif marker == 0xCC:
+            _refuse("an arithmetic-coded JPEG")
+        elif marker == 0xDD:
+            if len(body) >= 2 and int.from_bytes(body[:2], "big"):
+                _refuse("a JPEG with a restart interval (DRI)")
+        elif marker == 0xDA:
+            break
+    if frame is None:
+        _refuse("a JPEG whose scan comes before its frame header")
+    if not (1 <= h <= 16384 and 1 <= w <= 16384):
+        _refuse(f"a JPEG of {h} x {w} pixels (sizes are 1..16384)")
+    ids, factors = tuple(f[0] for f in frame), tuple(f[1] for f in frame)
+    if len(frame) == 1:
+        sampling = "grey"
+    elif len(frame) == 3:
+        if (not jfif and adobe is not None and adobe != 1) or (not jfif and adobe is None and ids == (82, 71, 66)):
+            _refuse("an RGB-coded JPEG (no YCbCr transform)")
+        sampling = {(0x22, 0x11, 0x11): "420", (0x11, 0x11, 0x11): "444"}.get(factors)
+        if sampling is None:
+            name = " (4:2:2)" if factors == (0x21, 0x11, 0x11) else ""
+            _refuse("a JPEG sampled " + ", ".join(f"{f >> 4}x{f & 15}" for f in factors) + name + ", neither 4:4:4 nor 4:2:0")
+    else:
+        _refuse(f"a JPEG of {len(frame)} components" + (" (CMYK or YCCK)" if len(frame) == 4 else ""))
+    if len(body) < 1 or len(body) != 4 + 2 * body[0]:
+        _refuse("a corrupt JPEG (a bad SOS segment)")
+    if body[0] != len(frame) or tuple(body[1 + 2 * i] for i in range(body[0])) != ids:
+        _refuse("a JPEG of several scans")
+    if tuple(body[-3:]) != (0, 63, 0):
+        _refuse("a JPEG whose scan is no whole sequential scan (a progressive one)")
+    select = [body[2 + 2 * i] for i in range(len(frame))]
+    if any(f[2] not in quant for f in frame) or any((s >> 4) not in huff or (0x10 | (s & 15)) not in huff for s in select):
+        _refuse("a corrupt JPEG (its scan uses a table that it does not define)")
+    m = _JPEG_NEXT_MARKER.search(data, at)
+    if m is None:  # the file ends inside its scan
+        end, marker = len(data) - (1 if data[-1:] == b"\xff" else 0), None
+    else:
+        end, j = m.start(), m.start() + 1
+        while j < len(data) and data[j] == 0xFF:  # fill bytes in front of the marker
+            j += 1
+        marker = data[j] if j < len(data) else None
+        if marker == 0:
+            _refuse("a corrupt JPEG (fill bytes inside its scan)")
+    if marker is not None and 0xD0 <= marker <= 0xD7:
+        _refuse("a JPEG with restart markers in its scan")
+    if marker is not None and marker != 0xD9:
+        _refuse("a JPEG of several scans")
+    return {"h": h, "w": w, "sampling": sampling, "tables": torch.tensor([quant[f[2]] for f in frame], dtype=torch.int32),
+            "huffman": tuple((huff[s >> 4], huff[0x10 | (s & 15)]) for s in select), "scan": data[at:end].replace(b"\xff\x00", b"\xff")}
+
+
+@functools.lru_cache(maxsize=64)
+def _jpeg_decode_table(counts, symbols):
+    """One code table as the kernels read it (include/w2e_jpeg.h): uint32 [W2E_JPEG_TABLE_WORDS]."""
+    lut, maxcode, valoff = np.zeros(512, np.uint16), np.full(18, -1, np.int32), np.zeros(17, np.int32)
+    code = k = 0
+    for length in range(1, 17):
+        n = counts[length - 1]
+        if n:
+            valoff[length] = k - code
+            if length <= 9:
+                for j in range(n):
+                    lut[(code + j) << (9 - length):(code + j + 1) << (9 - length)] = (length << 8) | symbols[k + j]
+            code, k = code + n, k + n
+            maxcode[length] = code - 1
+        code <<= 1
+    vals = np.zeros(256, np.uint8)
+    vals[:len(symbols)] = np.frombuffer(symbols, np.uint8)
+    t = np.zeros(_JPEG_TABLE_WORDS, np.uint32)
+    t[:256], t[256:274], t[274:291], t[320:384] = lut.view(np.uint32), maxcode.view(np.uint32), valoff.view(np.uint32), vals.view(np.uint32)
+    t.setflags(write=False)
+    return t
+
+
+def jpeg_decode_plan(batch, h, w, sampling, scan_bits, sub_bits=JPEG_SUB_BITS):
+    """w2e_jpeg_decode_plan as a dict: blocks per image, the MCU grid, subsequences per image, the workspace bytes of the two stages,
+    the most launches the relaxation can take, the coefficient elements per image.  Pure host."""
+    plan = (ctypes.c_int64 * 8)()
+    call("w2e_jpeg_decode_plan", batch, h, w, _sampling_id("jpeg_decode_plan", sampling), scan_bits, sub_bits, plan)
+    return {"blocks": plan[0], "mcus": (plan[2], plan[1]), "subsequences": plan[3], "workspace": plan[4], "pixel_workspace": plan[5],
+            "launches": plan[6], "coefficients": plan[7]}
+
+
+def _sampling_id(who, sampling):
+    if sampling not in JPEG_SAMPLINGS:
+        raise ValueError(f"{who}: sampling must be one of {JPEG_SAMPLINGS} (got {sampling!r})")
+    return JPEG_SAMPLINGS.index(sampling)
+
+
+def _check_sub_bits(who, sub_bits):
+    if not (isinstance(sub_bits, int) and not isinstance(sub_bits, bool) and 32 <= sub_bits <= 4096 and sub_bits % 32 == 0):
+        raise ValueError(f"{who}: sub_bits is a multiple of 32 in 32..4096 (got {sub_bits!r})")
+
+
+def _decode_device(who, device):
+    device = torch.device("cuda" if device is None else device)
+    if device.type != "cuda":
+        raise RuntimeError(f"{who}: device must be a GPU (got {device}) -- there is no CPU path")
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"{who}: the decoder runs on the GPU and none is available -- there is no CPU path (decode with Pillow instead)")
+    return torch.device("cuda", torch.cuda.current_device() if device.index is None else device.index)
+
+
+def _parsed_list(who, files):
+    single = isinstance(files, (bytes, bytearray, memoryview))
+    files = [files] if single else list(files)
+    return single, [jpeg_parse(f) for f in files]
+
+
+def _same_geometry(who, parsed):
+    keys = {(p["h"], p["w"], p["sampling"]) for p in parsed}
+    if len(keys) != 1:
+        raise ValueError(f"{who}: the files of one call must agree in height, width and sampling (got {sorted(keys)}); from_jpeg takes a mixed list")
+
+
+class _JpegBatch:
+    """The files of one geometry on the device: ONE upload (offsets and lengths, the code tables, the scans one after the other, each
+    padded with 0xFF to a multiple of 4 bytes), the plan, the workspace of stage 1."""
+
+    def __init__(self, parsed, device, sub_bits):
+        p0 = parsed[0]
+        self.b, self.h, self.w, self.sampling = len(parsed), p0["h"], p0["w"], _sampling_id("from_jpeg", p0["sampling"])
+        self.sub_bits, self.device = sub_bits, device
+        self.bits = [8 * len(p["scan"]) for p in parsed]
+        self.scan_bits = max(self.bits)
+        if self.scan_bits > _JPEG_MAX_SCAN_BITS:
+            raise ValueError(f"from_jpeg: a scan of {self.scan_bits // 8} bytes is longer than the decoder's 32-bit bit positions reach; decode it with Pillow")
+        meta, tables = np.zeros((self.b, 2), np.int64), np.zeros((self.b, 6, _JPEG_TABLE_WORDS), np.uint32)
+        scans, at = [], 0
+        for i, p in enumerate(parsed):
+            meta[i] = at, self.bits[i]
+            for c, (dc, ac) in enumerate(p["huffman"]):
+                tables[i, 2 * c], tables[i, 2 * c + 1] = _jpeg_decode_table(*dc), _jpeg_decode_table(*ac)
+            scans.append(p["scan"] + b"\xff" * (-len(p["scan"]) % 4))
+            at += len(scans[-1])
+        self.scan_bytes = at
+        head = meta.tobytes() + tables.tobytes()
+        blob = bytearray(head + b"".join(scans) + b"\xff" * 4)  # (never empty past the head: a pointer the library can check)
+        self.blob = torch.frombuffer(blob, dtype=torch.uint8).to(device)
+        self.meta, self.tables, self.scan = self.blob[:16 * self.b], self.blob[16 * self.b:len(head)], self.blob[len(head):]
+        self.plan = jpeg_decode_plan(self.b, self.h, self.w, p0["sampling"], self.scan_bits, sub_bits)
+        self.work = torch.empty(max(self.plan["workspace"], 16), dtype=torch.uint8, device=device)
+        self.quant = torch.zeros((self.b, 3, 64), dtype=torch.int32)
+        for i, p in enumerate(parsed):
+            self.quant[i, :p["tables"].shape[0]] = p["tables"]
+
+    def _args(self):
+        return (_p(self.scan), _p(self.meta), _p(self.tables), self.scan_bytes, self.b, self.h, self.w, self.sampling, self.scan_bits, self.sub_bits)
+
+    def relax(self):
+        """Launch w2e_jpeg_decode_sync until nothing changes; one 4-byte copy per launch.  Returns the number of launches."""
+        bound = self.plan["launches"]
+        changed = torch.zeros(bound, dtype=torch.int32, device=self.device)
+        for launch in range(bound):
+            call("w2e_jpeg_decode_sync", *self._args(), launch, _p(self.work), _p(changed[launch:]), stream_ptr())
+            if changed[launch].item() == 0:
+                return launch + 1
+        raise RuntimeError(f"jpeg decoder: the relaxation did not settle in its {bound} launches (a bug, not the file's fault)")
+
+    def states(self):
+        n = self.plan["subsequences"]
+        e = self.work[:8 * self.b * n].view(torch.int32).view(self.b, n, 2).cpu()
+        out = []
+        for i in range(self.b):
+            ni = max(1, -(-self.bits[i] // self.sub_bits))
+            out.append(torch.stack((e[i, :ni, 0], e[i, :ni, 1] >> 8, e[i, :ni, 1] & 255), dim=1))
+        return out
+
+    def coefficients(self):
+        coef = torch.empty((self.b, self.plan["blocks"], 64), dtype=torch.int16, device=self.device)
+        status = torch.empty((self.b,), dtype=torch.int32, device=self.device)
+        call("w2e_jpeg_decode_coefficients", *self._args(), _p(self.work), _p(coef), _p(status), stream_ptr())
+        return coef, status
+
+
+def _jpeg_raise(who, status, names=None):
+    for i, s in enumerate(status.tolist()):
+        if s:
+            why = "; ".join(text for bit, text in _JPEG_STATUS if s & bit)
+            raise ValueError(f"{who}: image {i if names is None else names[i]} has a corrupt scan (status {s}): {why}")
+
+
+def jpeg_decode_states(files, sub_bits=JPEG_SUB_BITS, device=None):
+    """The entropy decoder's relaxation on its own (for tests and for finding a fault): the bytes of one file, or a list of files of
+    one geometry -> (the converged entry state of every subsequence, int32 CPU [n, 3] = (bit position of the next symbol, block
+    position in the MCU, next zigzag index) per image; the number of launches it took)."""
+    _check_sub_bits("jpeg_decode_states", sub_bits)
+    single, parsed = _parsed_list("jpeg_decode_states", files)
+    _same_geometry("jpeg_decode_states", parsed)
+    device = _decode_device("jpeg_decode_states", device)
+    with torch.cuda.device(device):
+        batch = _JpegBatch(parsed, device, sub_bits)
+        launches = batch.relax()
+        states = batch.states()
+    return (states[0] if single else states), launches
+
+
+def jpeg_decode_coefficients(files, sub_bits=JPEG_SUB_BITS, device=None):
+    """Stage 1 of the decoder on its own: the bytes of one file -> int16 [blocks, 64] on the GPU; a list of files of one geometry ->
+    [B, blocks, 64].  Zigzag order, MCU scan order, the blocks outside the image included: for a file `to_jpeg` made, what
+    `jpeg_coefficients` returned.  The result is the same for every sub_bits.  A corrupt scan raises ValueError."""
+    _check_sub_bits("jpeg_decode_coefficients", sub_bits)
+    single, parsed = _parsed_list("jpeg_decode_coefficients", files)
+    _same_geometry("jpeg_decode_coefficients", parsed)
+    device = _decode_device("jpeg_decode_coefficients", device)
+    with torch.cuda.device(device):
+        batch = _JpegBatch(parsed, device, sub_bits)
+        batch.relax()
+        coef, status = batch.coefficients()
+        _jpeg_raise("jpeg_decode_coefficients", status.cpu())
+    return coef[0] if single else coef
+
+
+def _jpeg_pixels(coef, quant, h, w, sampling_id, plan):
+    b = coef.shape[0]
+    out = torch.empty((b, h, w, 3), dtype=torch.uint8, device=coef.device)
+    work = torch.empty(max(plan["pixel_workspace"], 16), dtype=torch.uint8, device=coef.device)
+    call("w2e_jpeg_pixels", _p(coef), _p(quant), b, h, w, sampling_id, _p(out), _p(work), stream_ptr())
+    return out
+
+
+def jpeg_pixels(coef, tables, h, w, sampling):
+    """Stage 2 of the decoder on its own: int16 [blocks, 64] or [B, blocks, 64] on the GPU (zigzag order, scan order) and the
+    quantisation tables (an integer tensor [components, 64], or [B, components, 64] for one set per image, natural order; CPU or GPU)
+    -> uint8 [h, w, 3] or [B, h, w, 3]: dequantisation, libjpeg's accurate integer inverse DCT, for "420" its fancy chroma
+    up-sampling, YCbCr -> RGB (grey: R = G = B = Y)."""
+    _on_gpu("jpeg_pixels", "coef", coef, torch.int16, (2, 3))
+    sid = _sampling_id("jpeg_pixels", sampling)
+    _check_size("jpeg_pixels", h), _check_size("jpeg_pixels", w)
+    c3 = coef.unsqueeze(0) if coef.ndim == 2 else coef
+    c3 = c3 if c3.is_contiguous() else c3.contiguous()
+    b = c3.shape[0]
+    with torch.cuda.device(coef.device):
+        plan = jpeg_decode_plan(b, h, w, sampling, 0)
+        if tuple(c3.shape[1:]) != (plan["blocks"], 64):
+            raise RuntimeError(f"jpeg_pixels: a {h} x {w} image sampled {sampling} has {plan['blocks']} blocks of 64 (got shape {tuple(coef.shape)})")
+        if not torch.is_tensor(tables) or tables.is_floating_point() or tables.ndim not in (2, 3) or tables.shape[-1] != 64:
+            raise RuntimeError("jpeg_pixels: tables is an integer tensor [components, 64] or [B, components, 64]")
+        t3 = tables.unsqueeze(0).expand(b, -1, -1) if tables.ndim == 2 else tables
+        if t3.shape[0] != b or t3.shape[1] != (1 if sampling == "grey" else 3):
+            raise RuntimeError(f"jpeg_pixels: tables of shape {tuple(tables.shape)} for {b} images of {1 if sampling == 'grey' else 3} components")
+        quant = torch.zeros((b, 3, 64), dtype=torch.int32, device=coef.device)
+        quant[:, :t3.shape[1]] = t3.to(device=coef.device, dtype=torch.int32)
+        out = _jpeg_pixels(c3, quant, h, w, sid, plan)
+    return out[0] if coef.ndim == 2 else out
+
+
+def from_jpeg(data, device=None, sub_bits=JPEG_SUB_BITS, stack=False):
+    """`np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))` on the GPU, byte for byte: the bytes of a baseline JPEG file ->
+    uint8 [H, W, 3]; a list of files -> a list of tensors (stack=True: one [B, H, W, 3] tensor; the sizes must then agree).  Only the
+    coded file crosses to the device.  Files of equal geometry (height, width, sampling) are decoded together as one batch: one
+    upload, the launches of the relaxation (`jpeg_decode_states`; one 4-byte copy each), then six launches.  What is in scope:
+    `jpeg_parse`, which refuses everything else on the host, before any launch.  A corrupt scan -- a file cut short, a damaged
+    byte -- raises ValueError; libjpeg's behaviour of warning and going on with grey blocks is NOT reproduced.
+    `to_tensor(from_jpeg(files, stack=True), 256)` is the reference's input side, file to normalised tensor, on the GPU."""
+    _check_sub_bits("from_jpeg", sub_bits)
+    single, parsed = _parsed_list("from_jpeg", data)
+    if stack and len({(p["h"], p["w"]) for p in parsed}) > 1:
+        raise ValueError(f"from_jpeg: stack=True needs images of one size (got {sorted({(p['h'], p['w']) for p in parsed})})")
+    if not parsed:
+        return torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=_decode_device("from_jpeg", device)) if stack else []
+    device = _decode_device("from_jpeg", device)
+    groups = {}
+    for i, p in enumerate(parsed):
+        groups.setdefault((p["h"], p["w"], p["sampling"]), []).append(i)
+    out, pending = [None] * len(parsed), []
+    with torch.cuda.device(device):
+        for members in groups.values():
+            batch = _JpegBatch([parsed[i] for i in members], device, sub_bits)
+            batch.relax()
+            coef, status = batch.coefficients()
+            pixels = _jpeg_pixels(coef, batch.quant.to(device), batch.h, batch.w, batch.sampling, batch.plan)
+            pending.append((members, status))
+            for j, i in enumerate(members):
+                out[i] = pixels[j]
+        for members, status in pending:
+            _jpeg_raise("from_jpeg", status.cpu(), members)
+    if single:
+        return out[0]
+    return torch.stack(out) if stack else out
+
+
+def load_image(fp, device=None):
+    """The counterpart of `save_image`: a path, or an object with read(), of a baseline JPEG file -> `from_jpeg` of its bytes, uint8
+    [H, W, 3] on the GPU."""
+    if hasattr(fp, "read"):
+        data = fp.read()
+    elif isinstance(fp, (str, os.PathLike)):
+        with open(fp, "rb") as f:
+            data = f.read()
+    else:
+        raise ValueError(f"load_image: fp is a path or an object with read() (got {type(fp).__name__})")
+    return from_jpeg(data, device=device)
 
 
 def clear_caches():
