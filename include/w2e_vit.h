@@ -22,7 +22,10 @@ extern "C" {
  *                 pre-activation h once, gelu(h) is never materialised)
  *   bias[N] or NULL is added;  residual[M,N] or NULL is added;
  *   gelu_grad_aux[M,N] or NULL: the result is multiplied by QuickGELU'(aux) (c_fc's input gradient).
- * lda/ldb/ldc are row strides in elements. */
+ * lda/ldb/ldc are row strides in elements.  residual and gelu_grad_aux are read at C's indices: element (i, j) at [i * ldc + j], so with
+ * ldc > N they are [M, ldc] buffers like C itself (the gaps are never read); with ldc == N, plain [M,N].
+ * K, lda, ldb (and N when trans_b = 0) are multiples of 4, a and b 16-byte aligned; a_gelu needs trans_b = 1; M = 0 launches nothing.
+ * K is split over slices of a multiple of 128 only when ldc == N (never with the "deterministic" option). */
 int w2e_gemm(const float* a, const float* b, float* c, int m, int n, int k, int lda, int ldb, int ldc, int trans_b,
              int a_gelu, const float* bias, const float* residual, const float* gelu_grad_aux, void* stream);
 /* The same with c_is_zero != 0: the caller guarantees C holds zeros, so a split-K launch (the skinny N = 768 shapes) adds

@@ -30,10 +30,11 @@ def _model(cfg, text=True):
                                             (200, 768, 2304, False), (37, 64, 32, True), (4, 512, 768, True), (130, 192, 68, False)])
 def test_gemm_vs_torch(m, n, k, trans_b):
     from where2edit_amd import vit_hip
-    a = torch.randn(m, k, device=DEV)
-    b = torch.randn(n, k, device=DEV) if trans_b else torch.randn(k, n, device=DEV)
-    bias = torch.randn(n, device=DEV)
-    res = torch.randn(m, n, device=DEV)
+    gen = torch.Generator().manual_seed(1000 * m + 10 * n + k + int(trans_b))
+    a = torch.randn(m, k, generator=gen).to(DEV)
+    b = (torch.randn(n, k, generator=gen) if trans_b else torch.randn(k, n, generator=gen)).to(DEV)
+    bias = torch.randn(n, generator=gen).to(DEV)
+    res = torch.randn(m, n, generator=gen).to(DEV)
     ref = (a.double() @ (b.double().t() if trans_b else b.double())) + bias.double() + res.double()
     c = vit_hip._gemm(a, b, trans_b, bias=bias, residual=res)
     assert_close(c, ref, 2e-6 * (k ** 0.5))
@@ -41,7 +42,7 @@ def test_gemm_vs_torch(m, n, k, trans_b):
         g = a.double() * torch.sigmoid(1.702 * a.double())
         c2 = vit_hip._gemm(a, b, True, a_gelu=True)
         assert_close(c2, g @ b.double().t(), 1e-5)
-    aux = torch.randn(m, n, device=DEV)
+    aux = torch.randn(m, n, generator=gen).to(DEV)
     s = torch.sigmoid(1.702 * aux.double())
     c3 = vit_hip._gemm(a, b, trans_b, gelu_grad_aux=aux)
     assert_close(c3, (a.double() @ (b.double().t() if trans_b else b.double())) * (s * (1 + 1.702 * aux.double() * (1 - s))), 1e-5)
@@ -49,22 +50,23 @@ def test_gemm_vs_torch(m, n, k, trans_b):
 
 def test_layernorm_and_attention_vs_torch():
     from where2edit_amd import vit_hip
-    x = torch.randn(3, 50, 768, device=DEV, requires_grad=True)
+    gen = torch.Generator().manual_seed(50768)
+    x = torch.randn(3, 50, 768, generator=gen).to(DEV).requires_grad_(True)
     ln = torch.nn.LayerNorm(768).to(DEV)
     with torch.no_grad():
-        ln.weight.normal_(1, 0.2), ln.bias.normal_(0, 0.2)
+        ln.weight.copy_(1 + 0.2 * torch.randn(768, generator=gen)), ln.bias.copy_(0.2 * torch.randn(768, generator=gen))
     ref = torch.nn.functional.layer_norm(x, (768,), ln.weight, ln.bias, 1e-5)
-    g = torch.randn_like(ref)
+    g = torch.randn(ref.shape, generator=gen).to(DEV)
     (gref,) = torch.autograd.grad(ref, x, g)
     ln.requires_grad_(False)
     y = vit_hip.layer_norm(x, ln)
     (gx,) = torch.autograd.grad(y, x, g)
     assert_close(y, ref, 1e-5), assert_close(gx, gref, 1e-5)
     for L, H in ((50, 12), (7, 2), (64, 1)):
-        qkv = torch.randn(2, L, 3 * H * 64, device=DEV, requires_grad=True)
+        qkv = torch.randn(2, L, 3 * H * 64, generator=gen).to(DEV).requires_grad_(True)
         q, k, v = qkv.view(2, L, 3, H, 64).permute(2, 0, 3, 1, 4)
         ref = ((q @ k.transpose(-1, -2) / 8).softmax(-1) @ v).transpose(1, 2).reshape(2, L, H * 64)
-        g = torch.randn_like(ref)
+        g = torch.randn(ref.shape, generator=gen).to(DEV)
         (gref,) = torch.autograd.grad(ref, qkv, g)
         out = vit_hip._Attention.apply(qkv, H)
         (gq,) = torch.autograd.grad(out, qkv, g)
