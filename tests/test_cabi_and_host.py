@@ -35,9 +35,158 @@ def test_library_exports_every_declared_symbol(lib):
     assert not missing, missing
 
 
-def test_ctypes_prototypes_cover_the_header():
-    from where2edit_amd import _lib, _lib_vit, irse_hip, run_attention
-    assert sorted(list(_lib._PROTOS) + list(_lib_vit.PROTOS) + list(run_attention.PROTOS) + list(irse_hip.PROTOS)) == _declared_symbols()
+SYNTHETIC_HEADER = r"""/* a header the reader has never seen; this comment holds a ; a ( and a fake
+ * declaration:  int w2e_fake(int);  none of which may be read */
+#ifndef W2E_SYNTH_H
+#define W2E_SYNTH_H
+#include <stdint.h>
+#define W2E_A (-1)
+#define W2E_B 0x7fff0000 /* c */
+#define W2E_C 12 // int w2e_fake2(int);
+#define W2E_PITCH(w) ((((w) + 1) + 15) & ~15)
+#define W2E_WORKSPACE(n, B) \
+    ((int64_t)(n) * 4 + \
+     (int64_t)(B) * 9)
+typedef struct {
+    const float* x;   /* device; */
+    int a, b;
+    int64_t* out;
+    double scale;
+} w2e_s;
+int w2e_version(void);
+const char* w2e_last_error(void);
+int w2e_three_lines(const float* x, float* const* ys, int64_t planes,
+                    int h, float slope,   // (a comment inside, with a , and a ) in it
+                    double eps, const char* name, void* stream);
+int w2e_takes_struct(const w2e_s* p, w2e_s* q, int n, const unsigned long long* seeds, const uint8_t* bytes);
+int64_t w2e_unnamed(int, const int*);
+#endif
+"""
+
+
+def test_header_reader_on_synthetic_text():
+    """where2edit_amd._abi.parse on literal header text (not the repository's headers); every expected value is written out here."""
+    from where2edit_amd import _abi
+    P, I, L, F, D, S = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_char_p
+    protos, structs, consts = _abi.parse(SYNTHETIC_HEADER, "synth.h")
+    assert consts == {"W2E_A": -1, "W2E_B": 0x7fff0000, "W2E_C": 12}  # no include guard, no function-like or multi-line macro
+    assert list(structs) == ["w2e_s"]
+    s = structs["w2e_s"]
+    assert issubclass(s, ctypes.Structure) and s._fields_ == [("x", P), ("a", I), ("b", I), ("out", P), ("scale", D)]
+    assert protos == {
+        "w2e_version": (I, []),
+        "w2e_last_error": (S, []),
+        "w2e_three_lines": (I, [P, P, L, I, F, D, S, P]),
+        "w2e_takes_struct": (I, [ctypes.POINTER(s), ctypes.POINTER(s), I, P, P]),
+        "w2e_unnamed": (L, [I, P]),
+    }
+    # a struct of an earlier header is known to the next one; one that is not known is no pointee of the mapping
+    assert _abi.parse("int w2e_next(const w2e_s* p);", "next.h", structs)[0] == {"w2e_next": (I, [ctypes.POINTER(s)])}
+    with pytest.raises(ValueError, match=r"next\.h: w2e_next: .*w2e_s\* p"):
+        _abi.parse("int w2e_next(const w2e_s* p);", "next.h")
+    # anything outside the fixed mapping raises, naming the header and the declaration
+    with pytest.raises(ValueError, match=r"bad\.h: w2e_bad: .*`long x`"):
+        _abi.parse("int w2e_ok(int a);\nint w2e_bad(int a, long x);", "bad.h")
+    with pytest.raises(ValueError, match=r"bad\.h: w2e_ret: .*size_t"):
+        _abi.parse("size_t w2e_ret(void);", "bad.h")
+    with pytest.raises(ValueError, match=r"bad\.h: struct w2e_t: .*short"):
+        _abi.parse("typedef struct { short a; } w2e_t;", "bad.h")
+    with pytest.raises(ValueError, match=r"bad\.h: w2e_chars: .*`char\* s`"):  # only `const char*` is a string
+        _abi.parse("int w2e_chars(char* s);", "bad.h")
+    # a declaration the pattern cannot read is an error, not a gap: here a function-pointer parameter
+    with pytest.raises(ValueError, match=r"bad\.h: cannot read the declaration of \['w2e_cb'\]"):
+        _abi.parse("int w2e_ok(int a);\nint w2e_cb(void (*f)(int), int n);", "bad.h")
+
+
+def _exported_symbols(path):
+    """The defined dynamic symbols of an ELF64 shared object (what `nm -D --defined-only` lists), read from its .dynsym."""
+    import struct
+    data = open(path, "rb").read()
+    assert data[:6] == b"\x7fELF\x02\x01", "not a little-endian ELF64 file"
+    shoff, = struct.unpack_from("<Q", data, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", data, 0x3A)
+    sections = [struct.unpack_from("<IIQQQQIIQQ", data, shoff + i * shentsize) for i in range(shnum)]
+    names = set()
+    for _, sh_type, _, _, offset, size, link, _, _, entsize in sections:
+        if sh_type != 11:  # SHT_DYNSYM
+            continue
+        strtab = sections[link][4]
+        for o in range(offset, offset + size, entsize):
+            st_name, _, _, st_shndx = struct.unpack_from("<IBBH", data, o)
+            if st_shndx != 0:
+                names.add(data[strtab + st_name:data.index(b"\0", strtab + st_name)].decode())
+    return names
+
+
+def test_ctypes_prototypes_cover_the_header(lib):
+    """Nothing skipped, nothing extra: the names read from include/*.h are the `w2e_` symbols libw2e.so exports."""
+    from where2edit_amd import _lib, build
+    exported = sorted(n for n in _exported_symbols(build.LIB_PATH) if n.startswith("w2e_"))
+    assert len(exported) >= 14 and "w2e_version" in exported
+    assert sorted(_lib._PROTOS) == exported
+    assert sorted(_lib._PROTOS) == _declared_symbols()
+
+
+def test_every_loaded_function_carries_its_derived_prototype(lib):
+    from where2edit_amd import _lib
+    loaded = _lib.load()
+    for name, (res, args) in _lib._PROTOS.items():
+        fn = getattr(loaded, name)
+        assert fn.restype is res and list(fn.argtypes) == args, name
+    assert _lib.DemodLayer is _lib.STRUCTS["w2e_demod_layer"] and _lib.header_version() == _lib.CONSTS["W2E_VERSION"]
+
+
+STRUCT_FIELDS = {  # (header, fields) as include/*.h declares them
+    "w2e_demod_layer": ("w2e.h", ["s", "wsq", "d", "cin", "cout"]),
+    "w2e_att_source": ("w2e_attention.h", ["feat", "wscaled", "style", "demod", "bias", "noise", "noise_w", "channels", "res"]),
+    "w2e_att_source_grad": ("w2e_attention.h", ["g_wscaled", "g_style", "g_bias", "g_noise_w"]),
+}
+
+
+def test_struct_layouts_are_the_c_compilers(tmp_path):
+    """sizeof and every offsetof of the three ABI structs, as a host C++ compiler lays them out from the headers, against the ctypes
+    Structures the reader derived."""
+    import shutil
+    import subprocess
+    from where2edit_amd import _lib
+    cxx = next((c for c in (os.environ.get("CXX"), "c++", "g++", "clang++") if c and shutil.which(c)), None)
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    assert set(_lib.STRUCTS) == set(STRUCT_FIELDS)
+    lines = ["#include <cstddef>", "#include <cstdio>"] + [f'#include "{h}"' for h in sorted({h for h, _ in STRUCT_FIELDS.values()})]
+    lines.append("int main() {")
+    for name, (_, fields) in STRUCT_FIELDS.items():
+        lines.append(f'    std::printf("{name} %zu\\n", sizeof({name}));')
+        lines += [f'    std::printf("{name}.{f} %zu\\n", offsetof({name}, {f}));' for f in fields]
+    lines += ["    return 0;", "}"]
+    (tmp_path / "layout.cpp").write_text("\n".join(lines) + "\n")
+    r = subprocess.run([cxx, "-I", os.path.join(ROOT, "include"), "-o", str(tmp_path / "layout"), str(tmp_path / "layout.cpp")],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = subprocess.run([str(tmp_path / "layout")], capture_output=True, text=True, timeout=30, check=True).stdout
+    want = dict((k, int(v)) for k, v in (ln.split() for ln in out.splitlines()))
+    for name, (_, fields) in STRUCT_FIELDS.items():
+        s = _lib.STRUCTS[name]
+        assert [f for f, _ in s._fields_] == fields, name
+        got = {name: ctypes.sizeof(s), **{f"{name}.{f}": getattr(s, f).offset for f in fields}}
+        assert got == {k: v for k, v in want.items() if k.split(".")[0] == name}, name
+
+
+def test_loading_the_library_imports_no_model_module(lib):
+    """The header reader needs neither torch nor a model; loading the library needs no model (run_attention pulls in stylegan2)."""
+    import subprocess
+    import sys
+    code = ("import sys\n"
+            "import where2edit_amd._abi\n"
+            "bad = [m for m in ('torch', 'where2edit_amd.run_attention') if m in sys.modules]\n"
+            "assert not bad, ('after _abi', bad)\n"
+            "import where2edit_amd._lib\n"
+            "where2edit_amd._lib.load()\n"
+            "bad = [m for m in ('where2edit_amd.run_attention', 'where2edit_amd.irse_hip', 'where2edit_amd.stylegan2') if m in sys.modules]\n"
+            "assert not bad, ('after load', bad)\n"
+            "print('clean')\n")
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.strip() == "clean", r.stderr[-2000:]
 
 
 def test_driver_build_hook_checks_hold_for_the_built_library(lib):

@@ -65,15 +65,15 @@ def test_argument_errors_are_raised_without_a_gpu():
 def test_kmeans_entry_points_are_declared():
     import ctypes
     import os
-    from where2edit_amd import build, run_attention
+    from where2edit_amd import _lib, build
     names = ("w2e_kmeans_plan", "w2e_kmeans_pass", "w2e_kmeans_reduce")
     header = open(os.path.join(os.path.dirname(build.PKG), "include", "w2e_attention.h")).read()
     lib = ctypes.CDLL(build.build(verbose=False))
     for n in names:
-        assert n in run_attention.PROTOS and f"int {n}(" in header and hasattr(lib, n)
+        assert n in _lib._PROTOS and f"int {n}(" in header and hasattr(lib, n)
     # argument validation happens before any HIP call
     lib.w2e_last_error.restype = ctypes.c_char_p
-    res, args = run_attention.PROTOS["w2e_kmeans_pass"]
+    res, args = _lib._PROTOS["w2e_kmeans_pass"]
     lib.w2e_kmeans_pass.restype, lib.w2e_kmeans_pass.argtypes = res, args
     d = ctypes.c_void_p(4096)
     assert lib.w2e_kmeans_pass(0, d, d, None, None, None, 0, d, 8, 1, 64, 4, 32, 33, None) != 0 and b"clusters <= 32" in lib.w2e_last_error()

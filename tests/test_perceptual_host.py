@@ -166,9 +166,11 @@ def test_trainer_refuses_two_identity_terms():
 
 @pytest.fixture(scope="module")
 def lib():
-    from where2edit_amd import build, irse_hip
+    from where2edit_amd import _lib, build
     lib = ctypes.CDLL(build.build(verbose=False))
-    irse_hip.declare(lib)
+    for name in ("w2e_maxpool2x2_fwd", "w2e_maxpool2x2_relu_bwd", "w2e_mse_relu_fwd"):
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = _lib._PROTOS[name]
     lib.w2e_last_error.restype = ctypes.c_char_p
     return lib
 

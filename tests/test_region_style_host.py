@@ -21,13 +21,13 @@ def lib():
 
 
 def test_symbols_are_declared_prototyped_and_exported_at_version_7(lib):
-    from where2edit_amd import _lib, run_attention
+    from where2edit_amd import _lib
     att = open(os.path.join(ROOT, "include", "w2e_attention.h")).read()
     main = open(os.path.join(ROOT, "include", "w2e.h")).read()
     for name in STYLE_SYMBOLS:
         assert re.search(r"^int\s+" + name + r"\(", att, re.M), f"{name} is not declared in include/w2e_attention.h"
-        assert name in run_attention.PROTOS, f"{name} has no ctypes prototype"
-        assert getattr(lib, name).argtypes == run_attention.PROTOS[name][1]
+        assert name in _lib._PROTOS, f"{name} has no ctypes prototype"
+        assert getattr(lib, name).argtypes == _lib._PROTOS[name][1]
     assert re.search(r"^int\s+w2e_adam_step\(", main, re.M) and "w2e_adam_step" in _lib._PROTOS
     assert lib.w2e_adam_step.argtypes == _lib._PROTOS["w2e_adam_step"][1]
     assert lib.w2e_version() == _lib.header_version() == 7

@@ -13,10 +13,10 @@ D = P(4096)  # a non-null, aligned dummy address: never dereferenced, every call
 def lib():
     from where2edit_amd import build
     lib = ctypes.CDLL(build.build(verbose=False))
-    from where2edit_amd import _lib_vit
+    from where2edit_amd import _lib
     for name in ("w2e_text_embed", "w2e_attn_causal_fwd", "w2e_text_pool"):
         fn = getattr(lib, name)
-        fn.restype, fn.argtypes = _lib_vit.PROTOS[name]
+        fn.restype, fn.argtypes = _lib._PROTOS[name]
     lib.w2e_last_error.restype = ctypes.c_char_p
     return lib
 

@@ -3,6 +3,7 @@ blend, CLIP ViT-B/32 image encoder) behind the reference's Python module/operato
 
 Layout:
   csrc/ + lib/libw2e.so   hand-written HIP (gfx950) behind the C ABI of include/w2e.h
+  _abi.py                 the prototypes, structs and integer constants of include/*.h, read from the headers (no hand-written copy)
   _lib.py                 ctypes door to that library (no fallback)
   functional.py           torch.autograd.Functions over the C ABI
   op/                     models/stylegan2/op seam: FusedLeakyReLU, fused_leaky_relu, upfirdn2d

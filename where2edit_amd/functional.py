@@ -13,7 +13,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib, profiling
-from ._lib import call, ptr, stream_ptr
+from ._lib import CONSTS, call, ptr, stream_ptr
 
 SQRT2 = math.sqrt(2.0)
 
@@ -159,7 +159,7 @@ def _upfirdn2d_raw(x, kernel, out_h, out_w, up, down, pad_x0, pad_y0, flip, act=
     return y
 
 
-_FirPlanFields = ctypes.c_int64 * 9  # W2E_FIR_PLAN_FIELDS
+_FirPlanFields = ctypes.c_int64 * CONSTS["W2E_FIR_PLAN_FIELDS"]
 
 
 def upfirdn_plan(planes, in_hw, out_hw, kernel_shape, up=1, down=1, pad_x0=0, planar=False, act=False, x_misalign=0, y_misalign=0):
@@ -262,7 +262,7 @@ def conv_pack(weight, scale, transpose, flip):
     return wp
 
 
-MODE_SAME, MODE_UP, MODE_DOWN = 0, 1, 2
+MODE_SAME, MODE_UP, MODE_DOWN = (CONSTS[f"W2E_CONV_{m}"] for m in ("SAME", "UP", "DOWN"))
 
 # ---- Winograd F(4x4,3x3) forms of the same-resolution layers (include/w2e.h, K1w / K1g).  Two own kernels, no vendor GEMM:
 #   form 4      the GEMM form for the WIDE layers: w2e_wino_pack_input (V in MFMA operand order) -> w2e_wino_gemm (the 36 contractions on fp32
@@ -297,11 +297,11 @@ def set_winograd(mode):
 FUSED_WGS = 0    # > 0: cap of the fused kernel's persistent grid (tests)
 GEMM_SPLITS = 0  # > 0: force w2e_wino_gemm's K split (tests); 0: the library's plan
 
-GENERATOR, ENCODER = 0, 1                         # W2E_WINO_GENERATOR / W2E_WINO_ENCODER: whose selection policy
-EPI_PLAIN, EPI_ACT, EPI_PRELU, EPI_DOT = range(4)  # W2E_WINO_EPI_*: the first three are the launchers' `act`
+GENERATOR, ENCODER = CONSTS["W2E_WINO_GENERATOR"], CONSTS["W2E_WINO_ENCODER"]  # whose selection policy
+EPI_PLAIN, EPI_ACT, EPI_PRELU, EPI_DOT = (CONSTS[f"W2E_WINO_EPI_{e}"] for e in ("PLAIN", "ACT", "PRELU", "DOT"))  # the first three are the launchers' `act`
 
 
-_WinoPlanFields = ctypes.c_int64 * 6  # W2E_WINO_PLAN_FIELDS
+_WinoPlanFields = ctypes.c_int64 * CONSTS["W2E_WINO_PLAN_FIELDS"]
 
 
 def wino_plan(family, b, k, n, h, w, epilogue=EPI_PLAIN, request=None, fused_allowed=True):

@@ -33,9 +33,9 @@ import re
 import numpy as np
 import torch
 
-from ._lib import call, stream_ptr
+from ._lib import CONSTS, call, stream_ptr
 
-PRECISION_BITS = 22  # W2E_IMAGE_PRECISION_BITS
+PRECISION_BITS = CONSTS["W2E_IMAGE_PRECISION_BITS"]
 FILTERS = ("bilinear", "nearest")
 
 
@@ -438,8 +438,8 @@ def save_image(x, fp, nrow=8, padding=2, value_range=(-1, 1), pad_value=0.0, qua
 # ---- JPEG decoding (include/w2e_jpeg.h, csrc/jpeg_decode.hip; DESIGN.md "K17c") ----
 JPEG_SAMPLINGS = ("420", "444", "grey")   # W2E_JPEG_420, W2E_JPEG_444, W2E_JPEG_GREY
 JPEG_SUB_BITS = 512                       # the default subsequence length of the entropy decoder, in bits: the fastest of 256 / 512 / 1024 at batch 8
-_JPEG_TABLE_WORDS = 384                   # W2E_JPEG_TABLE_WORDS
-_JPEG_MAX_SCAN_BITS = 0x7fff0000          # W2E_JPEG_MAX_SCAN_BITS
+_JPEG_TABLE_WORDS = CONSTS["W2E_JPEG_TABLE_WORDS"]
+_JPEG_MAX_SCAN_BITS = CONSTS["W2E_JPEG_MAX_SCAN_BITS"]
 _JPEG_SOF_NAMES = {0xC1: "an extended-sequential JPEG", 0xC2: "a progressive JPEG", 0xC3: "a lossless JPEG", 0xC5: "a hierarchical JPEG",
                    0xC6: "a hierarchical JPEG", 0xC7: "a hierarchical JPEG", 0xC9: "an arithmetic-coded JPEG", 0xCA: "an arithmetic-coded JPEG",
                    0xCB: "an arithmetic-coded JPEG", 0xCD: "an arithmetic-coded JPEG", 0xCE: "an arithmetic-coded JPEG", 0xCF: "an arithmetic-coded JPEG"}

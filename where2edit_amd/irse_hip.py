@@ -11,36 +11,10 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import functional as K
-from ._lib import call, ptr, stream_ptr
+from ._lib import CONSTS, call, ptr, stream_ptr
 from .derived import Holder, derived, drop
 
-_I = __import__("ctypes").c_int
-_P = __import__("ctypes").c_void_p
-_L = __import__("ctypes").c_int64
-_F = __import__("ctypes").c_float
-PROTOS = {
-    "w2e_conv3x3": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
-    "w2e_affine_act_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _P]),
-    "w2e_affine_act_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "w2e_channel_sums": (_I, [_P, _P, _P, _I, _I, _L, _P]),
-    "w2e_se_gate_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _P]),
-    "w2e_se_gate_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P]),
-    "w2e_se_apply_fwd": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _P]),
-    "w2e_se_apply_bwd": (_I, [_P, _P, _P, _P, _I, _I, _L, _P]),
-    "w2e_shortcut_add_bwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "w2e_upsample_add": (_I, [_P, _P, _P, _L, _I, _I, _I, _I, _P]),
-    "w2e_maxpool2x2_fwd": (_I, [_P, _P, _L, _I, _I, _P]),
-    "w2e_maxpool2x2_relu_bwd": (_I, [_P, _P, _P, _L, _I, _I, _I, _P]),
-    "w2e_mse_relu_fwd": (_I, [_P, _P, _I, _I, _L, _P, _P, _P, _I, _P, _P]),
-}
-
-MSE_PARTIALS = 1024  # W2E_MSE_PARTIALS (include/w2e_irse.h): the partials slab of w2e_mse_relu_fwd
-
-
-def declare(lib):
-    for name, (res, args) in PROTOS.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = res, args
+MSE_PARTIALS = CONSTS["W2E_MSE_PARTIALS"]  # the partials slab of w2e_mse_relu_fwd (include/w2e_irse.h)
 
 
 # ---------------------------------------------------------------------------------------------- raw kernel calls

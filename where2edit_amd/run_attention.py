@@ -35,50 +35,8 @@ from ._lib import call, ptr, stream_ptr
 from .derived import derived
 from .stylegan2 import EqualLinear, StyledConv
 
-_I32P = ctypes.c_void_p
-
-
-class _AttSourceGrad(ctypes.Structure):  # w2e_att_source_grad (include/w2e_attention.h)
-    _fields_ = [("g_wscaled", ctypes.c_void_p), ("g_style", ctypes.c_void_p), ("g_bias", ctypes.c_void_p), ("g_noise_w", ctypes.c_void_p)]
-
-
-class _AttSource(ctypes.Structure):  # w2e_att_source (include/w2e_attention.h)
-    _fields_ = [("feat", ctypes.c_void_p), ("wscaled", ctypes.c_void_p), ("style", ctypes.c_void_p), ("demod", ctypes.c_void_p),
-                ("bias", ctypes.c_void_p), ("noise", ctypes.c_void_p), ("noise_w", ctypes.c_void_p), ("channels", ctypes.c_int),
-                ("res", ctypes.c_int)]
-
-
-PROTOS = {
-    "w2e_cluster_assign": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                          ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "w2e_cluster_accumulate": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 5 + [ctypes.c_void_p]),
-    "w2e_attention_logits": (ctypes.c_int, [ctypes.POINTER(_AttSource), ctypes.c_int] + [ctypes.c_void_p] * 9 +
-                             [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "w2e_attention_demod": (ctypes.c_int, [ctypes.POINTER(_AttSource), ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_void_p]),
-    "w2e_cluster_pool": (ctypes.c_int, [ctypes.c_void_p] * 7 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_void_p]),
-    "w2e_attention_logits_train": (ctypes.c_int, [ctypes.POINTER(_AttSource), ctypes.c_int] + [ctypes.c_void_p] * 10 +
-                                   [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "w2e_attention_logits_bwd": (ctypes.c_int, [ctypes.POINTER(_AttSource), ctypes.POINTER(_AttSourceGrad), ctypes.c_int] +
-                                 [ctypes.c_void_p] * 14 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "w2e_cluster_pool_bwd": (ctypes.c_int, [ctypes.c_void_p] * 9 + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
-    # the offline k-means of clustering_feature.py (csrc/kmeans.hip)
-    "w2e_kmeans_plan": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int)] * 2),
-    "w2e_kmeans_pass": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_int64, ctypes.c_void_p] + [ctypes.c_int] * 6 +
-                        [ctypes.c_void_p]),
-    "w2e_kmeans_reduce": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
-    # the style branch (csrc/region_style.hip; host: region_style_hip.py)
-    "w2e_rstyle_linear_fwd": (ctypes.c_int, [ctypes.c_int] * 2 + [ctypes.c_void_p] * 11 + [ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]),
-    "w2e_rstyle_linear_dgrad": (ctypes.c_int, [ctypes.c_int] * 2 + [ctypes.c_void_p] * 11),
-    "w2e_rstyle_linear_wgrad": (ctypes.c_int, [ctypes.c_int] * 2 + [ctypes.c_void_p] * 12 + [ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]),
-    "w2e_rstyle_finish_fwd": (ctypes.c_int, [ctypes.c_int] * 2 + [ctypes.c_void_p] * 5 + [ctypes.c_float, ctypes.c_int] + [ctypes.c_void_p] * 3),
-    "w2e_rstyle_finish_bwd": (ctypes.c_int, [ctypes.c_int] * 2 + [ctypes.c_void_p] * 8 + [ctypes.c_float, ctypes.c_int, ctypes.c_void_p]),
-}
-
-
-def declare(lib):
-    for name, (res, args) in PROTOS.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = res, args
+_AttSource = _lib.STRUCTS["w2e_att_source"]            # include/w2e_attention.h
+_AttSourceGrad = _lib.STRUCTS["w2e_att_source_grad"]
 
 
 class GLU(nn.Module):
