@@ -57,7 +57,8 @@ extern "C" {
  * host-side queries).
  * Still 7, additive: w2e_jpeg_plan / w2e_jpeg_coefficients / w2e_jpeg_entropy (w2e_jpeg.h: Pillow's default JPEG, byte for byte).
  * Still 7, additive: w2e_jpeg_decode_plan / w2e_jpeg_decode_sync / w2e_jpeg_decode_coefficients / w2e_jpeg_pixels (w2e_jpeg.h: baseline
- * JPEG decoding, Pillow's pixels). */
+ * JPEG decoding, Pillow's pixels).
+ * Still 7, additive: w2e_png_plan / w2e_png_inflate / w2e_png_pixels (w2e_png.h: PNG decoding, Pillow's pixels). */
 #define W2E_VERSION 7
 
 int w2e_version(void);

@@ -23,6 +23,11 @@ config-5 pipeline with bytes at both ends against floats at both ends.
               the relaxation's worst case) on the host clock, with the number of launches; and the stages alone.  Lines go to
               --decode-out (profiles/jpeg_decode_bench.jsonl).
 
+  --png       from_png  B files -> uint8 pixels             vs  Pillow's decoder per file on one host core, then .to("cuda")
+              (B = 1, 8, 90 label-like 512 x 512 grey files of a few dozen flat regions, mode="raw"; one noisy 1024 x 1024 RGB file
+              and B = 8 of them, mode="RGB"; the files are written here, with zlib) on the host clock, and the two stages alone
+              (w2e_png_inflate, w2e_png_pixels) on device events.  Lines go to --png-out (profiles/png_decode_bench.jsonl).
+
 HIP events around `--inner` back-to-back calls of the Python entry point, device-synchronised, after a warm-up; the variants of a
 group alternate, `--repeats` times each (>= 5): the median, with min .. max as the spread a difference has to exceed.  `bytes` is
 what the call has to move (input + output), GB/s = bytes / median.  One JSON line per (group, variant, batch), appended to --out.
@@ -329,6 +334,81 @@ def bench_decode(a, lines):
                           subsequences=None if states is None else int(states.shape[0])))
 
 
+def bench_png(a, lines):
+    """from_png against what a caller does today (Pillow's decoder on one host core, then the pixels to the device): batches of
+    label-like 512 x 512 grey files and noisy 1024 x 1024 RGB files, written by tests/png_ref.py's writer (zlib level 6; the labels
+    unfiltered, the photographs with the Paeth filter).  Host-clock times of whole calls (both end synchronised); the two stages on
+    device events, one pair per repeat (stage 2 keeps rows in stage 1's output, so the pair runs together)."""
+    import io
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import png_ref as P
+    from where2edit_amd import image_io as I
+    try:
+        from PIL import Image
+    except ImportError:
+        Image = None
+    dev = torch.device("cuda", torch.cuda.current_device())
+
+    def label(seed):  # a few dozen flat regions: rectangles of ids 0..18 over one another
+        rng = np.random.default_rng(seed)
+        x = np.zeros((512, 512), np.uint8)
+        for _ in range(40):
+            y0, x0 = rng.integers(0, 448, 2)
+            x[y0:y0 + rng.integers(16, 200), x0:x0 + rng.integers(16, 200)] = rng.integers(0, 19)
+        return x
+
+    def pillow(files, mode):
+        images = [Image.open(io.BytesIO(f)) for f in files]
+        out = torch.from_numpy(np.stack([np.asarray(im.convert("RGB") if mode == "RGB" else im) for im in images])).to(dev)
+        torch.cuda.synchronize()
+        return out
+
+    def ours(files, mode):
+        out = I.from_png(files, mode=mode, stack=True)
+        torch.cuda.synchronize()
+        return out
+
+    cases = [("from_png_label_512", "raw", 0, [P.write_png(label(i), 0, filters=0, level=6) for i in range(90)], (1, 8, 90)),
+             ("from_png_rgb_1024", "RGB", 2, [P.write_png(photo_u8(1, 1024, 1024, i)[0].numpy(), 2, filters=4, level=6) for i in range(8)], (1, 8))]
+    for group, mode, colour, files, batches in cases:
+        for b in batches:
+            fs = files[:b]
+            coded = sum(len(f) for f in fs)
+            want = ours(fs, mode)
+            variants = {"hip": lambda: ours(fs, mode)}
+            extra = {"coded_bytes": coded, "mode": mode}
+            if Image is not None:
+                variants["pillow_then_h2d"] = lambda: pillow(fs, mode)
+                extra["equal_to_pillow"] = bool(torch.equal(want, pillow(fs, mode)))
+            t = time_host(variants, a.repeats)
+            for name, ms in t.items():
+                lines.append(line(group, name, b, ms, coded + want.numel(), **extra))
+            # the stages alone
+            parsed = [I.png_parse(f) for f in fs]
+            h, w = parsed[0]["h"], parsed[0]["w"]
+            plan = I.png_plan(b, h, w, colour, 8, mode)
+            meta, sizes, data, total = I._png_upload([p["stream"] for p in parsed], [plan["size"]] * b, dev)
+            raw = torch.empty((b, plan["pitch"]), dtype=torch.uint8, device=dev)
+            status = torch.empty((b,), dtype=torch.int32, device=dev)
+            out = torch.empty(want.shape, dtype=torch.uint8, device=dev)
+            ms1, ms2 = [], []
+            for rep in range(a.repeats + 2):
+                e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+                e[0].record()
+                I.call("w2e_png_inflate", I._p(data), I._p(meta), I._p(sizes), total, b, I._p(raw), plan["pitch"], I._p(status), I.stream_ptr())
+                e[1].record()
+                I.call("w2e_png_pixels", I._p(raw), plan["pitch"], None, b, h, w, colour, 8, I.PNG_MODES.index(mode), I._p(out), I._p(status), I.stream_ptr())
+                e[2].record()
+                torch.cuda.synchronize()
+                if rep >= 2:
+                    ms1.append(e[0].elapsed_time(e[1])), ms2.append(e[1].elapsed_time(e[2]))
+            assert int(status.abs().sum()) == 0 and torch.equal(out, want)
+            lines.append(line("png_stage" + group[8:], "inflate", b, ms1, sum(len(p["stream"]) for p in parsed) + b * plan["size"]))
+            lines.append(line("png_stage" + group[8:], "pixels", b, ms2, b * plan["size"] + want.numel()))
+            del raw, out, want
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=20)
@@ -339,6 +419,8 @@ def main():
     ap.add_argument("--jpeg-out", default=os.path.join(ROOT, "profiles", "jpeg_bench.jsonl"))
     ap.add_argument("--decode", action="store_true", help="only the JPEG decoder; lines go to --decode-out")
     ap.add_argument("--decode-out", default=os.path.join(ROOT, "profiles", "jpeg_decode_bench.jsonl"))
+    ap.add_argument("--png", action="store_true", help="only the PNG decoder; lines go to --png-out")
+    ap.add_argument("--png-out", default=os.path.join(ROOT, "profiles", "png_decode_bench.jsonl"))
     a = ap.parse_args()
     if a.repeats < 5:
         raise SystemExit("--repeats must be >= 5: the spread is part of the result")
@@ -350,13 +432,15 @@ def main():
             bench_jpeg(a, lines)
         elif a.decode:
             bench_decode(a, lines)
+        elif a.png:
+            bench_png(a, lines)
         else:
             bench_calls(a, lines)
             if not a.skip_pipeline:
                 bench_pipeline(a, lines)
     for ln in lines:
         print(json.dumps(ln))
-    out = a.jpeg_out if a.jpeg else (a.decode_out if a.decode else a.out)
+    out = a.jpeg_out if a.jpeg else (a.decode_out if a.decode else (a.png_out if a.png else a.out))
     if out:
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
         with open(out, "a") as f:

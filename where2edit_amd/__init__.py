@@ -22,7 +22,8 @@ Layout:
   evaluation.py           the region mask's IoU against parsing labels (utils.py:639-726): MaskIoU, calculate_iou
   image_io.py             bytes in, bytes out on csrc/image.hip: Pillow's resize + ToTensor / Normalize (to_tensor, label_ids, resize_u8),
                           torchvision's save_image up to the PNG encoder (to_bytes), its .jpg file (to_jpeg, save_image), and
-                          baseline JPEG files in (from_jpeg, load_image) on csrc/jpeg.hip and csrc/jpeg_decode.hip
+                          baseline JPEG files in (from_jpeg, load_image) on csrc/jpeg.hip and csrc/jpeg_decode.hip, PNG files in
+                          (from_png, load_png, read_image) on csrc/png.hip
 """
 __version__ = "0.1.0"
 
@@ -61,9 +62,10 @@ def r1_penalty(discriminator, real, return_logits=False):
 
 
 # where2edit_amd.evaluation's public names, importable from the package (resolved on first use: importing the package stays light)
-_EVALUATION = ("CELEBAMASK_REGIONS", "region_lut", "binarise", "attention_with_text", "MaskIoU", "calculate_iou")
+_EVALUATION = ("CELEBAMASK_REGIONS", "region_lut", "binarise", "attention_with_text", "MaskIoU", "calculate_iou", "celebamask_samples")
 _IMAGE_IO = ("resample_tables", "resize_u8", "to_tensor", "label_ids", "to_bytes", "jpeg_tables", "jpeg_header", "jpeg_coefficients", "to_jpeg",
-             "save_image", "jpeg_parse", "jpeg_decode_states", "jpeg_decode_coefficients", "jpeg_pixels", "from_jpeg", "load_image")
+             "save_image", "jpeg_parse", "jpeg_decode_states", "jpeg_decode_coefficients", "jpeg_pixels", "from_jpeg", "load_image",
+             "png_parse", "png_plan", "png_inflate", "png_pixels", "from_png", "load_png", "read_image")
 
 
 def __getattr__(name):

@@ -234,3 +234,29 @@ def calculate_iou(samples, g_ema, mapper, text_features, *, attention_layer=13, 
         metric.update(masks, label)  # (binarisation happens inside the counting kernel)
         seen += batch
     return metric.compute()
+
+
+def celebamask_samples(img_dir, label_dir, batch=8, device=None):
+    """The samples of `calculate_iou` from CelebAMask-HQ as the reference lays it out (utils.py:570-587): image i is
+    `img_dir/{i}.jpg`, its parsing label `label_dir/{i}.png`, i = 0 .. (number of files in img_dir) - 1.  A generator of
+    (uint8 [B,H,W,3] images, uint8 [B,H,W] label ids), both decoded on the GPU (image_io.from_jpeg / from_png(mode="raw")), `batch`
+    files at a time.  With calculate_iou(..., e4e=..., label_resize="bilinear") the evaluation runs from the files to the IoU without
+    Pillow."""
+    import os
+
+    from .image_io import from_jpeg, from_png
+    if not (isinstance(batch, int) and batch >= 1):
+        raise ValueError(f"celebamask_samples: batch is a positive integer (got {batch!r})")
+    count = len([name for name in os.listdir(img_dir) if os.path.isfile(os.path.join(img_dir, name))])
+
+    def read(path):
+        with open(path, "rb") as f:
+            return f.read()
+
+    for first in range(0, count, batch):
+        ids = range(first, min(first + batch, count))
+        images = from_jpeg([read(os.path.join(img_dir, f"{i}.jpg")) for i in ids], device=device, stack=True)
+        labels = from_png([read(os.path.join(label_dir, f"{i}.png")) for i in ids], mode="raw", device=device, stack=True)
+        if labels.ndim != 3:
+            raise ValueError(f"celebamask_samples: the labels {first}.png .. are no grey or palette files (decoded shape {tuple(labels.shape)})")
+        yield images, labels

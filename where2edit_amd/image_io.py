@@ -22,13 +22,21 @@ CelebAMask-HQ images, utils.py:573-587).  `from_jpeg` / `load_image` decode a ba
 (csrc/jpeg_decode.hip; DESIGN.md "K17c"): the host walks the markers (`jpeg_parse`), only the coded file crosses to the device, the
 Huffman stream is decoded in parallel by self-synchronisation, then inverse DCT, chroma up-sampling and colour conversion.
 
-PNG stays with the caller.  GPU only: there is no CPU fallback (tests/imageio_ref.py, tests/jpeg_ref.py and tests/jpeg_decode_ref.py
-are the numpy restatements the kernels are tested against)."""
+PNG files in.  The other files the reference reads are PNGs: the CelebAMask-HQ parsing labels (`Image.open(str(i) + '.png')`,
+utils.py:573-587) and the demo's portraits (show_demo/try_demo.py:66-68, 96-97).  `from_png` / `load_png` decode a non-interlaced 8-bit
+(palette: 1 to 8 bits) file on the device to Pillow's own pixels, `mode="RGB"` for `convert("RGB")` and `mode="raw"` for the ids of a
+label (csrc/png.hip, csrc/png_core.h; DESIGN.md "K17d"): the host walks the chunks and verifies their CRCs (`png_parse`), only the
+compressed stream and the palette cross to the device, one wave inflates each stream of a batch, then the row filters are undone.
+`read_image` takes either kind of file.  `save_image` writes JPEG only, as the reference does.
+
+GPU only: there is no CPU fallback (tests/imageio_ref.py, tests/jpeg_ref.py, tests/jpeg_decode_ref.py and
+tests/png_ref.py are the numpy restatements the kernels are tested against)."""
 import ctypes
 import functools
 import math
 import os
 import re
+import zlib
 
 import numpy as np
 import torch
@@ -818,6 +826,260 @@ def load_image(fp, device=None):
     else:
         raise ValueError(f"load_image: fp is a path or an object with read() (got {type(fp).__name__})")
     return from_jpeg(data, device=device)
+
+
+# ---- PNG decoding (include/w2e_png.h, csrc/png.hip, csrc/png_core.h; DESIGN.md "K17d") ----
+PNG_MODES = ("RGB", "raw")   # W2E_PNG_MODE_RGB, W2E_PNG_MODE_RAW
+_PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+_PNG_COLOURS = {0: "grey", 2: "RGB", 3: "palette", 4: "grey + alpha", 6: "RGBA"}
+_PNG_CHANNELS = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}
+_PNG_STATUS = tuple((CONSTS["W2E_PNG_STATUS_" + name], text) for name, text in (
+    ("TYPE", "a block of type 3"), ("STORED", "a stored block whose LEN and NLEN disagree"), ("LENGTHS", "a bad code-length set"),
+    ("CODE", "a code that matches no symbol (or length symbol 286 / 287, distance symbol 30 / 31)"),
+    ("DISTANCE", "a distance that reaches before the start of the output"), ("INPUT", "the input ends inside the stream"),
+    ("SHORT", "the stream ends before the image's size"), ("LONG", "the stream goes on past the image's size"),
+    ("ADLER", "the Adler-32 of the inflated bytes is not the stream's"), ("FILTER", "a filter byte above 4")))
+
+
+def _png_refuse(what):
+    raise ValueError(f"png_parse: the file is {what}, which the GPU decoder does not take; decode it with Pillow")
+
+
+def _check_zlib_header(who, z):
+    """The two header bytes of a zlib stream (RFC 1950): method 8, a window of at most 32 KiB, the check bits, no preset dictionary."""
+    if len(z) < 2 or (z[0] & 15) != 8 or (z[0] >> 4) > 7 or ((z[0] << 8) | z[1]) % 31:
+        raise ValueError(f"{who}: the compressed data does not begin with a zlib header")
+    if z[1] & 32:
+        raise ValueError(f"{who}: the zlib stream asks for a preset dictionary, which the GPU decoder does not take; decode it with Pillow")
+
+
+def png_parse(data):
+    """The host side of the PNG decoder: walk the chunks of a file and hand back what the kernels need, as a dict -- `h`, `w`, `colour`
+    (the PNG colour type: 0 grey, 2 RGB, 3 palette, 4 grey + alpha, 6 RGBA), `depth`, `palette` (uint32 CPU [256], entry = R | G << 8 |
+    B << 16, 0 past the end of PLTE; None without a palette) and `stream` (the IDAT payloads joined: one zlib stream).
+    Every chunk's CRC is verified (a bad one is a ValueError, as with Pillow).  In scope: non-interlaced, 8 bits for colour types 0, 2,
+    4, 6, and 1 / 2 / 4 / 8 bits for the palette; sizes 1..16384.  Adam7 interlacing, 16 bits, grey below 8 bits, APNG, a preset
+    dictionary and larger sizes raise a ValueError that names what the file is and ends "decode it with Pillow".  tRNS and every
+    other ancillary chunk are ignored, as `convert("RGB")` ignores transparency.  A damaged zlib stream is NOT refused here: it goes to
+    the kernels as it is and their status refuses it."""
+    if isinstance(data, (bytearray, memoryview)):
+        data = bytes(data)
+    if not isinstance(data, bytes):
+        raise ValueError(f"png_parse: data is the bytes of a PNG file (got {type(data).__name__})")
+    if data[:8] != _PNG_SIGNATURE:
+        _png_refuse("no PNG (it does not begin with the PNG signature)")
+    at, head, palette, parts, ended = 8, None, None, [], False
+    while not ended:
+        if at + 8 > len(data):
+            raise ValueError("png_parse: the file is cut inside a chunk")
+        size, kind = int.from_bytes(data[at:at + 4], "big"), data[at + 4:at + 8]
+        if at + 12 + size > len(data):
+            raise ValueError(f"png_parse: the file is cut inside its {kind.decode('latin-1')} chunk")
+        body = data[at + 8:at + 8 + size]
+        if zlib.crc32(data[at + 4:at + 8 + size]) != int.from_bytes(data[at + 8 + size:at + 12 + size], "big"):
+            raise ValueError(f"png_parse: the CRC of the {kind.decode('latin-1')} chunk at byte {at} is wrong")
+        at += 12 + size
+        if head is None and kind != b"IHDR":
+            raise ValueError("png_parse: the first chunk is not IHDR")
+        if kind == b"IHDR":
+            if size != 13 or head is not None:
+                raise ValueError("png_parse: a bad IHDR chunk")
+            head = (int.from_bytes(body[0:4], "big"), int.from_bytes(body[4:8], "big")) + tuple(body[8:13])
+        elif kind == b"PLTE":
+            if size % 3 or not 3 <= size <= 768:
+                raise ValueError("png_parse: a bad PLTE chunk")
+            rgb = np.frombuffer(body, np.uint8).reshape(-1, 3).astype(np.uint32)
+            palette = torch.zeros(256, dtype=torch.int32)
+            palette[:len(rgb)] = torch.from_numpy((rgb[:, 0] | (rgb[:, 1] << 8) | (rgb[:, 2] << 16)).astype(np.int32))
+        elif kind == b"acTL":
+            _png_refuse("an animated PNG (APNG)")
+        elif kind == b"IDAT":
+            parts.append(body)
+        elif kind == b"IEND":
+            ended = True
+    w, h, depth, colour, compression, filtering, interlace = head
+    if colour not in _PNG_COLOURS or compression or filtering or depth not in (1, 2, 4, 8, 16) or interlace > 1:
+        raise ValueError(f"png_parse: a bad IHDR chunk (colour type {colour}, depth {depth}, compression {compression}, filter {filtering}, interlace {interlace})")
+    if interlace:
+        _png_refuse("an interlaced PNG (Adam7)")
+    if depth == 16:
+        _png_refuse("a 16-bit PNG")
+    if depth < 8 and colour == 0:
+        _png_refuse(f"a {depth}-bit grey PNG")
+    if depth < 8 and colour != 3:
+        raise ValueError(f"png_parse: a bad IHDR chunk ({_PNG_COLOURS[colour]} at {depth} bits)")
+    if not (1 <= h <= 16384 and 1 <= w <= 16384):
+        _png_refuse(f"a PNG of {h} x {w} pixels (sizes are 1..16384)")
+    if colour == 3 and palette is None:
+        raise ValueError("png_parse: a palette PNG without a PLTE chunk")
+    if not parts:
+        raise ValueError("png_parse: a PNG without an IDAT chunk")
+    stream = b"".join(parts)
+    _check_zlib_header("png_parse", stream)
+    return {"h": h, "w": w, "colour": colour, "depth": depth, "palette": palette if colour == 3 else None, "stream": stream}
+
+
+def _png_mode_id(who, mode):
+    if mode not in PNG_MODES:
+        raise ValueError(f"{who}: mode must be one of {PNG_MODES} (got {mode!r})")
+    return PNG_MODES.index(mode)
+
+
+def png_plan(batch, h, w, colour, depth=8, mode="RGB"):
+    """w2e_png_plan as a dict: the bytes of a filtered row (filter byte included), the inflated size of an image, the pitch of the
+    filtered-row buffer, the channels and bytes of the output, the filters' pixel distance, stage 1's LDS bound and stage 2's band.
+    Pure host."""
+    plan = (ctypes.c_int64 * 8)()
+    call("w2e_png_plan", batch, h, w, colour, depth, _png_mode_id("png_plan", mode), plan)
+    return {"row_bytes": plan[0], "size": plan[1], "pitch": plan[2], "channels": plan[3], "out_bytes": plan[4], "bpp": plan[5], "lds": plan[6],
+            "band": plan[7]}
+
+
+def _png_upload(streams, sizes, device):
+    """ONE upload: offsets and lengths, the inflated sizes, then the streams one after the other, each padded to a multiple of 4."""
+    b = len(streams)
+    meta, at, parts = np.zeros((b, 3), np.int64), 0, []
+    for i, z in enumerate(streams):
+        meta[i] = at, len(z), sizes[i]
+        parts.append(bytes(z) + b"\0" * (-len(z) % 4))
+        at += len(parts[-1])
+    head = np.ascontiguousarray(meta[:, :2]).tobytes() + np.ascontiguousarray(meta[:, 2]).tobytes()
+    blob = torch.frombuffer(bytearray(head + b"".join(parts) + b"\0" * 4), dtype=torch.uint8).to(device)
+    return blob[:16 * b], blob[16 * b:24 * b], blob[24 * b:], at
+
+
+def _png_inflate(streams, sizes, pitch, device):
+    b = len(streams)
+    meta, dsizes, data, total = _png_upload(streams, sizes, device)
+    raw = torch.empty((b, pitch), dtype=torch.uint8, device=device)
+    status = torch.empty((b,), dtype=torch.int32, device=device)
+    call("w2e_png_inflate", _p(data), _p(meta), _p(dsizes), total, b, _p(raw), pitch, _p(status), stream_ptr())
+    return raw, status
+
+
+def _png_raise(who, status, names=None):
+    for i, s in enumerate(status.tolist()):
+        if s:
+            why = "; ".join(text for bit, text in _PNG_STATUS if s & bit)
+            raise ValueError(f"{who}: image {i if names is None else names[i]} has a corrupt stream (status {s}): {why}")
+
+
+def png_inflate(streams, sizes, device=None):
+    """Stage 1 of the decoder on its own (for tests and for finding a fault): a zlib stream (bytes) and the exact number of bytes it
+    inflates to -> uint8 [size] on the GPU; a list of streams and a list of sizes -> a list of tensors, inflated as ONE batch in one
+    launch.  A corrupt stream, or one that inflates to another size, raises ValueError."""
+    single = isinstance(streams, (bytes, bytearray, memoryview))
+    streams, sizes = ([bytes(streams)], [sizes]) if single else ([bytes(z) for z in streams], list(sizes))
+    if len(streams) != len(sizes) or any(not (isinstance(n, int) and 0 <= n <= 0x7fffffff) for n in sizes):
+        raise ValueError(f"png_inflate: one size (an integer in 0..2^31-1) per stream (got {len(streams)} streams and sizes {sizes!r})")
+    for z in streams:
+        _check_zlib_header("png_inflate", z)
+    device = _decode_device("png_inflate", device)
+    if not streams:
+        return []
+    with torch.cuda.device(device):
+        raw, status = _png_inflate(streams, sizes, -(-max(max(sizes), 1) // 4) * 4, device)
+        _png_raise("png_inflate", status.cpu())
+    out = [raw[i, :n] for i, n in enumerate(sizes)]
+    return out[0] if single else out
+
+
+def _png_pixels(raw, palette, h, w, colour, depth, mode_id, plan, status):
+    b = raw.shape[0]
+    shape = (b, h, w) if plan["channels"] == 1 else (b, h, w, plan["channels"])
+    out = torch.empty(shape, dtype=torch.uint8, device=raw.device)
+    call("w2e_png_pixels", _p(raw), raw.shape[1], _p(palette), b, h, w, colour, depth, mode_id, _p(out), _p(status), stream_ptr())
+    return out
+
+
+def png_pixels(raw, h, w, colour, depth=8, palette=None, mode="RGB"):
+    """Stage 2 of the decoder on its own: the filtered rows of an image, uint8 [h * row bytes] (each row its filter byte and its
+    bytes, as a zlib stream inflates to them) or [B, h * row bytes] on the GPU -> the pixels of `mode`: "RGB" uint8 [h, w, 3]; "raw"
+    [h, w] for grey and palette (the index), [h, w, 2 | 3 | 4] for grey + alpha, RGB and RGBA.  palette: an integer tensor [n, 3] (n <=
+    256) or [B, n, 3] of R, G, B for colour 3.  The input is left as it was.  A filter byte above 4 raises ValueError."""
+    _on_gpu("png_pixels", "raw", raw, torch.uint8, (1, 2))
+    mode_id = _png_mode_id("png_pixels", mode)
+    _check_size("png_pixels", h), _check_size("png_pixels", w)
+    r2 = raw.unsqueeze(0) if raw.ndim == 1 else raw
+    b = r2.shape[0]
+    with torch.cuda.device(raw.device):
+        plan = png_plan(b, h, w, colour, depth, mode)
+        if r2.shape[1] != plan["size"]:
+            raise RuntimeError(f"png_pixels: a {h} x {w} image of colour type {colour} at {depth} bits has {plan['size']} filtered bytes (got shape {tuple(raw.shape)})")
+        table = None
+        if colour == 3:
+            if not torch.is_tensor(palette) or palette.is_floating_point() or palette.ndim not in (2, 3) or palette.shape[-1] != 3 or palette.shape[-2] > 256:
+                raise RuntimeError("png_pixels: palette is an integer tensor [n, 3] or [B, n, 3] with n <= 256 for colour type 3")
+            p3 = (palette.unsqueeze(0).expand(b, -1, -1) if palette.ndim == 2 else palette).to(device=raw.device, dtype=torch.int32)
+            if p3.shape[0] != b:
+                raise RuntimeError(f"png_pixels: palette of shape {tuple(palette.shape)} for {b} images")
+            table = torch.zeros((b, 256), dtype=torch.int32, device=raw.device)
+            table[:, :p3.shape[1]] = (p3[..., 0] & 255) | ((p3[..., 1] & 255) << 8) | ((p3[..., 2] & 255) << 16)
+        work = torch.zeros((b, plan["pitch"]), dtype=torch.uint8, device=raw.device)  # (the kernel keeps rows in its input)
+        work[:, :plan["size"]] = r2
+        status = torch.zeros((b,), dtype=torch.int32, device=raw.device)
+        out = _png_pixels(work, table, h, w, colour, depth, mode_id, plan, status)
+        _png_raise("png_pixels", status.cpu())
+    return out[0] if raw.ndim == 1 else out
+
+
+def from_png(data, mode="RGB", device=None, stack=False):
+    """`np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))` (mode="RGB": uint8 [H, W, 3], grey replicated, alpha dropped, the
+    palette looked up) or `np.asarray(Image.open(io.BytesIO(data)))` (mode="raw": [H, W] for grey and palette files -- the ids a
+    parsing label holds -- and [H, W, 2 | 3 | 4] for grey + alpha, RGB and RGBA) on the GPU, byte for byte: the bytes of a PNG file
+    -> a tensor; a list of files -> a list of tensors (stack=True: one tensor; the shapes must then agree).  Only the compressed
+    stream and the palette cross to the device.  Files of equal geometry (height, width, colour type, depth) are decoded together:
+    one upload and two launches per group, all streams of a group inflating at once, one wave each.  What is in scope: `png_parse`,
+    which refuses everything else on the host, before any launch.  A corrupt stream raises ValueError; the status is read once per
+    call, after every group is launched.
+    `label_ids(from_png(files, mode="raw", stack=True), 64)` is the reference's label side, file to ids, on the GPU."""
+    mode_id = _png_mode_id("from_png", mode)
+    single = isinstance(data, (bytes, bytearray, memoryview))
+    parsed = [png_parse(f) for f in ([data] if single else list(data))]
+    device = _decode_device("from_png", device)
+    groups = {}
+    for i, p in enumerate(parsed):
+        groups.setdefault((p["h"], p["w"], p["colour"], p["depth"]), []).append(i)
+    if stack and len({(h, w, png_plan(1, h, w, c, d, mode)["channels"]) for h, w, c, d in groups}) > 1:
+        raise ValueError(f"from_png: stack=True needs images of one shape (got the (h, w, colour type, depth) {sorted(groups)})")
+    if not parsed:
+        return torch.empty((0, 0, 0, 3) if mode == "RGB" else (0, 0, 0), dtype=torch.uint8, device=device) if stack else []
+    out, pending = [None] * len(parsed), []
+    with torch.cuda.device(device):
+        for (h, w, colour, depth), members in groups.items():
+            plan = png_plan(len(members), h, w, colour, depth, mode)
+            raw, status = _png_inflate([parsed[i]["stream"] for i in members], [plan["size"]] * len(members), plan["pitch"], device)
+            palette = torch.stack([parsed[i]["palette"] for i in members]).to(device) if colour == 3 else None
+            pixels = _png_pixels(raw, palette, h, w, colour, depth, mode_id, plan, status)
+            pending.append((members, status))
+            for j, i in enumerate(members):
+                out[i] = pixels[j]
+        for members, status in pending:
+            _png_raise("from_png", status.cpu(), members)
+    if single:
+        return out[0]
+    return torch.stack(out) if stack else out
+
+
+def _read_file(who, fp):
+    if hasattr(fp, "read"):
+        return fp.read()
+    if isinstance(fp, (str, os.PathLike)):
+        with open(fp, "rb") as f:
+            return f.read()
+    raise ValueError(f"{who}: fp is a path or an object with read() (got {type(fp).__name__})")
+
+
+def load_png(fp, mode="RGB", device=None):
+    """A path, or an object with read(), of a PNG file -> `from_png` of its bytes."""
+    return from_png(_read_file("load_png", fp), mode=mode, device=device)
+
+
+def read_image(fp, device=None):
+    """`Image.open(fp).convert("RGB")` (show_demo/try_demo.py:96-97) for a PNG or a baseline JPEG file, by its first eight bytes: a
+    path, or an object with read() -> uint8 [H, W, 3] on the GPU, through `from_png(mode="RGB")` or `from_jpeg`."""
+    data = _read_file("read_image", fp)
+    return from_png(data, mode="RGB", device=device) if data[:8] == _PNG_SIGNATURE else from_jpeg(data, device=device)
 
 
 def clear_caches():
