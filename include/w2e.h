@@ -58,7 +58,9 @@ extern "C" {
  * Still 7, additive: w2e_jpeg_plan / w2e_jpeg_coefficients / w2e_jpeg_entropy (w2e_jpeg.h: Pillow's default JPEG, byte for byte).
  * Still 7, additive: w2e_jpeg_decode_plan / w2e_jpeg_decode_sync / w2e_jpeg_decode_coefficients / w2e_jpeg_pixels (w2e_jpeg.h: baseline
  * JPEG decoding, Pillow's pixels).
- * Still 7, additive: w2e_png_plan / w2e_png_inflate / w2e_png_pixels (w2e_png.h: PNG decoding, Pillow's pixels). */
+ * Still 7, additive: w2e_png_plan / w2e_png_inflate / w2e_png_pixels (w2e_png.h: PNG decoding, Pillow's pixels).
+ * Still 7, additive: w2e_png_encode_plan / w2e_png_deflate_plan / w2e_png_filter / w2e_png_deflate (w2e_png.h: PNG encoding, Pillow's
+ * filtered rows, the library's own chunked deflate). */
 #define W2E_VERSION 7
 
 int w2e_version(void);

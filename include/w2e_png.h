@@ -1,4 +1,5 @@
-/* w2e_png.h -- C ABI of the PNG decoder (csrc/png.hip, csrc/png_core.h) in libw2e.so (gfx950): the pixels of Pillow's
+/* w2e_png.h -- C ABI of the PNG decoder (csrc/png.hip, csrc/png_core.h) and, further down, of the PNG encoder in libw2e.so (gfx950).
+ * Decoding: the pixels of Pillow's
  * Image.open(fp) and Image.open(fp).convert("RGB") for the files the reference reads -- the CelebAMask-HQ parsing labels and the
  * demo's portraits (DESIGN.md "K17d").  PNG is lossless, so the answer is exact.
  * In scope: non-interlaced; colour types 0 (grey), 2 (RGB), 4 (grey + alpha), 6 (RGBA) at 8 bits, colour type 3 (palette) at 1, 2, 4
@@ -66,6 +67,55 @@ int w2e_png_inflate(const uint8_t* streams, const int64_t* meta, const int64_t* 
  * status: int32 [batch]; W2E_PNG_STATUS_FILTER is ORed into it (the row is then taken as unfiltered). */
 int w2e_png_pixels(uint8_t* raw, int64_t raw_pitch, const uint32_t* palette, int batch, int h, int w, int colour, int depth, int mode,
                    uint8_t* out, int32_t* status, void* stream);
+
+/* ---- encoding (csrc/png_encode.hip, csrc/png_deflate_core.h; DESIGN.md "K17e") ----
+ * The file of `Image.fromarray(x).save(fp, "PNG")` for Pillow's modes L, LA, RGB and RGBA up to the compressed bytes: the filtered rows
+ * are Pillow's byte for byte (its adaptive filter choice), the deflate stream is this library's own.  Non-interlaced, 8 bits, colour types
+ * 0 / 4 / 2 / 6 for 1 / 2 / 3 / 4 channels.  The host (image_io.to_png) adds the signature, IHDR, the framing of the one IDAT and IEND.
+ * Out of scope: palette and sub-8-bit output, 16 bits, interlacing, ancillary chunks, matches across chunk boundaries, Pillow's
+ * `optimize` and `compress_level`.  Two stages, each reachable on its own:
+ *   1. w2e_png_filter: pixels -> filtered rows, filter byte included (one launch; one wave per row scores None, Sub, Up and Paeth by the
+ *      sum of min(v, 256 - v) over the row's filtered bytes and takes the smallest; on a tie Up wins over Sub, otherwise the lower number);
+ *   2. w2e_png_deflate: filtered bytes -> one zlib stream per image (two launches).  The input is cut into chunks of W2E_PNG_CHUNK bytes;
+ *      no match reaches before its chunk, so one workgroup codes one chunk into a slot of the workspace: ONE deflate block, the cheapest
+ *      of stored, fixed and dynamic by bit cost, then -- unless it is the image's last, which carries BFINAL -- an empty stored block
+ *      (zlib's sync-flush marker) that ends the slot on a byte boundary.  The second launch sums the slot lengths of an image in order,
+ *      gathers the slots behind the two header bytes and appends the Adler-32, combined from the chunks' (s1, s2, length).
+ * The conventions above hold: nothing inside allocates, copies, memsets or uses a global atomic; no workgroup waits on another; the same
+ * input gives the same bytes on every run, and the bytes of tests/png_deflate_host.cpp, which runs the same core with one lane. */
+#define W2E_PNG_CHUNK 32768        /* bytes of input that one workgroup of stage 2 codes */
+#define W2E_PNG_SLOT 32780         /* bytes of a chunk's slot: the stored form's W2E_PNG_CHUNK + 10, rounded up to a multiple of 4 */
+#define W2E_PNG_DEFLATE_LDS 61440  /* an upper bound of the LDS of one workgroup of stage 2, in bytes: two chunks per CU */
+
+/* w2e_png_deflate_plan (pure host): a batch of buffers of at most max_size bytes (0..2^31-1) each.  plan has 4 entries:
+ *   plan[0]  chunks per image: max(1, ceil(max_size / W2E_PNG_CHUNK))
+ *   plan[1]  W2E_PNG_SLOT
+ *   plan[2]  workspace bytes: batch * plan[0] * (W2E_PNG_SLOT + 4 * W2E_PNG_CHUNK + 16) -- slots, token lists, (length, s1, s2, n)
+ *   plan[3]  the largest possible stream, from the stored form: max_size + 10 * plan[0] + 6 */
+int w2e_png_deflate_plan(int batch, int64_t max_size, int64_t* plan);
+
+/* w2e_png_encode_plan (pure host).  channels: 1 (L), 2 (LA), 3 (RGB) or 4 (RGBA).  plan has 8 entries:
+ *   plan[0]  bytes of one filtered row, its filter byte included: 1 + w * channels
+ *   plan[1]  the filtered size of one image: h * plan[0]
+ *   plan[2]  raw_pitch: plan[1] rounded up to a multiple of 4
+ *   plan[3]  chunks per image          \
+ *   plan[4]  slot bytes per chunk       | w2e_png_deflate_plan(batch, plan[1])
+ *   plan[5]  workspace bytes            |
+ *   plan[6]  the largest possible stream/
+ *   plan[7]  out_pitch: plan[6] rounded up to a multiple of 4
+ * h and w are in 1..W2E_IMAGE_MAX_SIZE (w2e_image.h), batch in 0..65535. */
+int w2e_png_encode_plan(int batch, int h, int w, int channels, int64_t* plan);
+
+/* Stage 1.  x: uint8 [batch, h, w, channels].  raw: uint8 [batch, raw_pitch], raw_pitch >= plan[1]: bytes [0, plan[1]) of every row are
+ * written, never any other. */
+int w2e_png_filter(const uint8_t* x, int batch, int h, int w, int channels, uint8_t* raw, int64_t raw_pitch, void* stream);
+
+/* Stage 2.  raw: uint8 [batch, raw_pitch] (4-byte aligned, raw_pitch a multiple of 4 and >= max_size).  sizes: int64 [batch], the bytes of
+ * buffer b (taken as 0 below 0 and as max_size above it).  out: uint8 [batch, out_pitch] (4-byte aligned, out_pitch a multiple of 4 and >=
+ * plan[3] of w2e_png_deflate_plan(batch, max_size)); lengths: int64 [batch], the bytes of stream b.  work: plan[2] bytes, 8-byte aligned;
+ * it needs no initialisation. */
+int w2e_png_deflate(const uint8_t* raw, int64_t raw_pitch, const int64_t* sizes, int batch, int64_t max_size, uint8_t* out, int64_t out_pitch,
+                    int64_t* lengths, uint8_t* work, int64_t work_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -28,6 +28,12 @@ config-5 pipeline with bytes at both ends against floats at both ends.
               and B = 8 of them, mode="RGB"; the files are written here, with zlib) on the host clock, and the two stages alone
               (w2e_png_inflate, w2e_png_pixels) on device events.  Lines go to --png-out (profiles/png_decode_bench.jsonl).
 
+  --png-encode  to_png  uint8 [B,H,W,C] -> B files          vs  .cpu(), then Pillow's PNG save per image on one host core
+              (B = 1 and 8 photo-like 1024 x 1024 RGB canvases; B = 1 and 90 label-like 512 x 512 grey images; B = 8 noise canvases,
+              the worst case: every chunk stored, and the second copy) on the host clock, with the bytes of the files of both; and the
+              two stages alone (w2e_png_filter, w2e_png_deflate) on device events.  Lines go to --png-encode-out
+              (profiles/png_encode_bench.jsonl).
+
 HIP events around `--inner` back-to-back calls of the Python entry point, device-synchronised, after a warm-up; the variants of a
 group alternate, `--repeats` times each (>= 5): the median, with min .. max as the spread a difference has to exceed.  `bytes` is
 what the call has to move (input + output), GB/s = bytes / median.  One JSON line per (group, variant, batch), appended to --out.
@@ -409,6 +415,79 @@ def bench_png(a, lines):
             del raw, out, want
 
 
+def bench_png_encode(a, lines):
+    """to_png against what a caller does today (the pixels to the host, Pillow's PNG encoder on one host core).  Host-clock times of
+    whole calls; the two stages on device events, one pair per repeat."""
+    import io
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import png_encode_ref as E
+    from where2edit_amd import image_io as I
+    try:
+        from PIL import Image
+    except ImportError:
+        Image = None
+    dev = torch.device("cuda", torch.cuda.current_device())
+
+    def pillow(x):
+        host = x.cpu().numpy()
+        files = []
+        for i in range(host.shape[0]):
+            buf = io.BytesIO()
+            Image.fromarray(host[i, :, :, 0] if host.shape[3] == 1 else host[i]).save(buf, format="PNG")
+            files.append(buf.getvalue())
+        return files
+
+    labels = torch.from_numpy(np.stack([E.label(512, 512, regions=19, name=f"bench{i}") for i in range(90)]))
+    noise = torch.from_numpy(np.stack([E.noise(1024, 1024, name=f"bench{i}") for i in range(8)]))
+    cases = [("to_png_rgb_1024", photo_u8(8, 1024, 1024, 0), (1, 8)), ("to_png_label_512", labels, (1, 90)), ("to_png_noise_1024", noise, (8,))]
+    for group, images, batches in cases:
+        for b in batches:
+            x = images[:b].to(dev)
+            files = I.to_png(x)
+            back = I.from_png(files, mode="raw", stack=True)
+            assert torch.equal(back.reshape(x.shape), x)
+            variants = {"hip": lambda: I.to_png(x)}
+            extra = {"file_bytes": sum(len(f) for f in files)}
+            if Image is not None:
+                variants["d2h_then_pillow"] = lambda: pillow(x)
+                theirs = pillow(x)
+                extra["pillow_file_bytes"] = sum(len(f) for f in theirs)
+                extra["rows_equal_to_pillow"] = all(zlib_rows(E, f) == zlib_rows(E, g) for f, g in zip(files[:2], theirs[:2]))
+            t = time_host(variants, a.repeats)
+            for name, ms in t.items():
+                lines.append(line(group, name, b, ms, x.numel() + extra["file_bytes"], **extra))
+            # the stages alone
+            _, h, w, c = x.shape
+            plan = I.png_encode_plan(b, h, w, c)
+            raw = torch.empty((b, plan["pitch"]), dtype=torch.uint8, device=dev)
+            sizes = torch.full((b,), plan["size"], dtype=torch.int64, device=dev)
+            out = torch.empty((b, plan["out_pitch"]), dtype=torch.uint8, device=dev)
+            lengths = torch.empty((b,), dtype=torch.int64, device=dev)
+            work = torch.empty((plan["workspace"],), dtype=torch.uint8, device=dev)
+            ms1, ms2 = [], []
+            for rep in range(a.repeats + 2):
+                e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+                e[0].record()
+                I.call("w2e_png_filter", I._p(x), b, h, w, c, I._p(raw), plan["pitch"], I.stream_ptr())
+                e[1].record()
+                I.call("w2e_png_deflate", I._p(raw), plan["pitch"], I._p(sizes), b, plan["size"], I._p(out), plan["out_pitch"], I._p(lengths), I._p(work),
+                       plan["workspace"], I.stream_ptr())
+                e[2].record()
+                torch.cuda.synchronize()
+                if rep >= 2:
+                    ms1.append(e[0].elapsed_time(e[1])), ms2.append(e[1].elapsed_time(e[2]))
+            coded = int(lengths.sum())
+            lines.append(line("png_encode_stage" + group[6:], "filter", b, ms1, x.numel() + b * plan["size"]))
+            lines.append(line("png_encode_stage" + group[6:], "deflate", b, ms2, b * plan["size"] + coded, chunks=b * plan["chunks"]))
+            del raw, out, work
+
+
+def zlib_rows(E, f):
+    import zlib
+    return zlib.decompress(E.idat_payload(f)[0])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=20)
@@ -421,6 +500,8 @@ def main():
     ap.add_argument("--decode-out", default=os.path.join(ROOT, "profiles", "jpeg_decode_bench.jsonl"))
     ap.add_argument("--png", action="store_true", help="only the PNG decoder; lines go to --png-out")
     ap.add_argument("--png-out", default=os.path.join(ROOT, "profiles", "png_decode_bench.jsonl"))
+    ap.add_argument("--png-encode", action="store_true", help="only the PNG encoder; lines go to --png-encode-out")
+    ap.add_argument("--png-encode-out", default=os.path.join(ROOT, "profiles", "png_encode_bench.jsonl"))
     a = ap.parse_args()
     if a.repeats < 5:
         raise SystemExit("--repeats must be >= 5: the spread is part of the result")
@@ -434,13 +515,15 @@ def main():
             bench_decode(a, lines)
         elif a.png:
             bench_png(a, lines)
+        elif a.png_encode:
+            bench_png_encode(a, lines)
         else:
             bench_calls(a, lines)
             if not a.skip_pipeline:
                 bench_pipeline(a, lines)
     for ln in lines:
         print(json.dumps(ln))
-    out = a.jpeg_out if a.jpeg else (a.decode_out if a.decode else (a.png_out if a.png else a.out))
+    out = a.jpeg_out if a.jpeg else (a.decode_out if a.decode else (a.png_out if a.png else (a.png_encode_out if a.png_encode else a.out)))
     if out:
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
         with open(out, "a") as f:

@@ -65,7 +65,8 @@ def r1_penalty(discriminator, real, return_logits=False):
 _EVALUATION = ("CELEBAMASK_REGIONS", "region_lut", "binarise", "attention_with_text", "MaskIoU", "calculate_iou", "celebamask_samples")
 _IMAGE_IO = ("resample_tables", "resize_u8", "to_tensor", "label_ids", "to_bytes", "jpeg_tables", "jpeg_header", "jpeg_coefficients", "to_jpeg",
              "save_image", "jpeg_parse", "jpeg_decode_states", "jpeg_decode_coefficients", "jpeg_pixels", "from_jpeg", "load_image",
-             "png_parse", "png_plan", "png_inflate", "png_pixels", "from_png", "load_png", "read_image")
+             "png_parse", "png_plan", "png_inflate", "png_pixels", "from_png", "load_png", "read_image", "png_encode_plan", "png_filter", "png_deflate",
+             "to_png", "save_png")
 
 
 def __getattr__(name):

@@ -29,8 +29,14 @@ label (csrc/png.hip, csrc/png_core.h; DESIGN.md "K17d"): the host walks the chun
 compressed stream and the palette cross to the device, one wave inflates each stream of a batch, then the row filters are undone.
 `read_image` takes either kind of file.  `save_image` writes JPEG only, as the reference does.
 
-GPU only: there is no CPU fallback (tests/imageio_ref.py, tests/jpeg_ref.py, tests/jpeg_decode_ref.py and
-tests/png_ref.py are the numpy restatements the kernels are tested against)."""
+PNG files out.  `to_png` / `save_png` are the lossless way out: torchvision's `save_image(x, "name.png")` ends in Pillow's PNG encoder,
+and `to_png` is that encoder on the device up to the compressed bytes (csrc/png_encode.hip, csrc/png_deflate_core.h; DESIGN.md
+"K17e").  The filtered rows are Pillow's byte for byte (`png_filter`: its choice among None, Sub, Up and Paeth for every row); the
+deflate stream is the library's own (`png_deflate`: independent 32 KiB chunks, one workgroup each, joined as zlib's sync flush joins
+them), so any reader gets the pixels back exactly and only the compressed data crosses to the host.
+
+GPU only: there is no CPU fallback (tests/imageio_ref.py, tests/jpeg_ref.py, tests/jpeg_decode_ref.py,
+tests/png_ref.py and tests/png_encode_ref.py are the numpy restatements the kernels are tested against)."""
 import ctypes
 import functools
 import math
@@ -428,7 +434,8 @@ def to_jpeg(x, quality=75):
 def save_image(x, fp, nrow=8, padding=2, value_range=(-1, 1), pad_value=0.0, quality=75):
     """`torchvision.utils.save_image(x, fp, nrow=, padding=, normalize=True, range=value_range, pad_value=)` (0.8.2) for a `.jpg`:
     fp32 [B,C,H,W] (C = 1 or 3) on the GPU -> to_bytes' canvas -> to_jpeg -> the file.  fp: a path ending in .jpg / .jpeg, or an
-    object with write() (the reference only ever writes JPEG; PNG is not implemented)."""
+    object with write() (the reference only ever writes JPEG).  This function writes no PNG and refuses a `.png` path: a lossless
+    file of the same canvas goes through `save_png`."""
     if isinstance(fp, (str, os.PathLike)):
         if os.path.splitext(os.fspath(fp))[1].lower() not in (".jpg", ".jpeg"):
             raise ValueError(f"save_image: {os.fspath(fp)!r} does not end in .jpg or .jpeg; PNG (and every other format) is not implemented")
@@ -1080,6 +1087,160 @@ def read_image(fp, device=None):
     path, or an object with read() -> uint8 [H, W, 3] on the GPU, through `from_png(mode="RGB")` or `from_jpeg`."""
     data = _read_file("read_image", fp)
     return from_png(data, mode="RGB", device=device) if data[:8] == _PNG_SIGNATURE else from_jpeg(data, device=device)
+
+
+# ---- PNG encoding (include/w2e_png.h "encoding", csrc/png_encode.hip, csrc/png_deflate_core.h; DESIGN.md "K17e") ----
+_PNG_COLOUR_OF_CHANNELS = {1: 0, 2: 4, 3: 2, 4: 6}   # L, LA, RGB, RGBA
+_PNG_GUESS = (5, 8)  # to_png's first copy takes 5/8 of the filtered size per image: above a photograph's rate (about 0.55 at 1024 x 1024)
+
+
+def png_encode_plan(batch, h, w, channels):
+    """w2e_png_encode_plan as a dict: the bytes of a filtered row (filter byte included), the filtered size of an image, the pitch of
+    the filtered-row buffer, the chunks per image, the slot bytes per chunk, the workspace bytes, the largest possible stream (from the
+    stored form: size + 10 per chunk + 6) and the pitch of the stream buffer.  Pure host."""
+    plan = (ctypes.c_int64 * 8)()
+    call("w2e_png_encode_plan", batch, h, w, channels, plan)
+    return {"row_bytes": plan[0], "size": plan[1], "pitch": plan[2], "chunks": plan[3], "slot": plan[4], "workspace": plan[5], "stream": plan[6],
+            "out_pitch": plan[7]}
+
+
+def _png_encode_input(who, x):
+    _on_gpu(who, "x", x, torch.uint8, (3, 4))
+    if not 1 <= x.shape[-1] <= 4:
+        raise RuntimeError(f"{who}: images are [H,W,C] or [B,H,W,C] with C = 1 (L), 2 (LA), 3 (RGB) or 4 (RGBA), channels last (got shape {tuple(x.shape)})")
+    x4 = x.unsqueeze(0) if x.ndim == 3 else x
+    _check_size(who, x4.shape[1]), _check_size(who, x4.shape[2])
+    return x4 if x4.is_contiguous() else x4.contiguous()
+
+
+def _png_filter(x4, plan):
+    b, h, w, c = x4.shape
+    raw = torch.empty((b, plan["pitch"]), dtype=torch.uint8, device=x4.device)
+    call("w2e_png_filter", _p(x4), b, h, w, c, _p(raw), plan["pitch"], stream_ptr())
+    return raw
+
+
+def png_filter(x):
+    """Stage 1 of the encoder on its own (for tests and for finding a fault): uint8 [H,W,C] or [B,H,W,C] on the GPU -> uint8
+    [H * (1 + W * C)] or [B, H * (1 + W * C)], the rows a PNG's zlib stream holds: per row the filter byte, then the filtered bytes.
+    The filter of every row is the one Pillow chooses (None, Sub, Up or Paeth by the smallest sum of min(v, 256 - v))."""
+    x4 = _png_encode_input("png_filter", x)
+    with torch.cuda.device(x4.device):
+        plan = png_encode_plan(*x4.shape)
+        raw = _png_filter(x4, plan)[:, :plan["size"]]
+    return raw[0] if x.ndim == 3 else raw
+
+
+def _png_deflate(raw, sizes, max_size):
+    """raw: uint8 [b, pitch] on the GPU; sizes: int64 [b] on the GPU -> (streams uint8 [b, out_pitch], lengths int64 [b])."""
+    b = raw.shape[0]
+    plan = (ctypes.c_int64 * 4)()
+    call("w2e_png_deflate_plan", b, max_size, plan)
+    pitch = -(-plan[3] // 4) * 4
+    out = torch.empty((b, pitch), dtype=torch.uint8, device=raw.device)
+    lengths = torch.empty((b,), dtype=torch.int64, device=raw.device)
+    work = torch.empty((plan[2],), dtype=torch.uint8, device=raw.device)
+    call("w2e_png_deflate", _p(raw), raw.shape[1], _p(sizes), b, max_size, _p(out), pitch, _p(lengths), _p(work), plan[2], stream_ptr())
+    return out, lengths
+
+
+def _png_fetch(out, lengths, guess):
+    """Streams and lengths to the host in ONE copy while no stream is longer than `guess`; a second copy fetches the rest."""
+    b = out.shape[0]
+    guess = min(out.shape[1], guess)
+    packed = torch.cat((lengths.view(torch.uint8).view(b, 8), out[:, :guess]), dim=1).cpu().numpy()
+    sizes = packed[:, :8].copy().view("<i8").ravel().tolist()
+    data = packed[:, 8:]
+    if max(sizes) > guess:
+        data = out[:, :max(sizes)].cpu().numpy()
+    return [data[i, :n].tobytes() for i, n in enumerate(sizes)]
+
+
+def png_deflate(raw_list, device=None):
+    """Stage 2 of the encoder on its own: a list of buffers (uint8 tensors of one dimension, bytes or numpy arrays; any lengths, empty
+    included) -> a list of zlib streams (bytes), coded as ONE batch in two launches.  Every stream inflates to its buffer with any
+    inflate; the bytes are this library's own, the same on every run: chunks of 32 KiB coded independently, one deflate block each
+    (stored, fixed or dynamic, whichever is shortest), joined by empty stored blocks as zlib's sync flush joins them."""
+    if isinstance(raw_list, (bytes, bytearray, memoryview)) or torch.is_tensor(raw_list):
+        raise ValueError("png_deflate: raw_list is a list of buffers (got one buffer)")
+    buffers = []
+    for i, r in enumerate(raw_list):
+        if torch.is_tensor(r):
+            if r.dtype != torch.uint8 or r.ndim != 1:
+                raise RuntimeError(f"png_deflate: buffer {i} must be a uint8 tensor of one dimension (got {r.dtype}, shape {tuple(r.shape)})")
+            if not r.is_cuda:
+                raise RuntimeError(f"png_deflate: buffer {i} must be on the GPU (got {r.device}): move it with .to('cuda') first -- there is no CPU path")
+        else:
+            r = np.frombuffer(bytes(r), np.uint8) if not isinstance(r, np.ndarray) else np.ascontiguousarray(r, np.uint8).ravel()
+        buffers.append(r)
+    if any(len(r) > 0x7fffffff for r in buffers):
+        raise ValueError("png_deflate: a buffer has at most 2^31-1 bytes")
+    tensors = [r for r in buffers if torch.is_tensor(r)]
+    device = _decode_device("png_deflate", tensors[0].device if tensors and device is None else device)
+    if not buffers:
+        return []
+    with torch.cuda.device(device):
+        sizes = [len(r) for r in buffers]
+        pitch = -(-max(max(sizes), 1) // 4) * 4
+        if tensors:
+            raw = torch.zeros((len(buffers), pitch), dtype=torch.uint8, device=device)
+            for i, r in enumerate(buffers):
+                raw[i, :sizes[i]] = r if torch.is_tensor(r) else torch.from_numpy(r.copy()).to(device)
+        else:  # ONE upload
+            host = np.zeros((len(buffers), pitch), np.uint8)
+            for i, r in enumerate(buffers):
+                host[i, :sizes[i]] = r
+            raw = torch.from_numpy(host).to(device)
+        out, lengths = _png_deflate(raw, torch.tensor(sizes, dtype=torch.int64).to(device), max(sizes))
+        return _png_fetch(out, lengths, out.shape[1])
+
+
+def _png_chunk(name, body):
+    return len(body).to_bytes(4, "big") + name + body + zlib.crc32(name + body).to_bytes(4, "big")
+
+
+def to_png(x):
+    """`Image.fromarray(x).save(fp, format="PNG")` of images on the GPU, up to the compressed bytes: uint8 [H,W,C] -> bytes, uint8
+    [B,H,W,C] -> a list of B bytes (`[]` for B = 0).  C = 1, 2, 3, 4 give PNG colour types 0, 4, 2, 6 at 8 bits: Pillow's modes L, LA,
+    RGB, RGBA.  The file is non-interlaced, with one IDAT and no ancillary chunk.  Its IDAT inflates to Pillow's filtered rows byte for
+    byte -- the same filter for every row -- so any reader gets the pixels back exactly; the compressed bytes are this library's own
+    (`png_deflate`), within a few per cent of Pillow's size on photographs and labels (DESIGN.md "K17e").  Three launches for the whole
+    batch; what crosses to the host is the compressed data and the lengths, in ONE copy as long as no image compresses to more than
+    5/8 of its filtered size; past that (noise) a second copy fetches the rest.  The host adds the signature, IHDR, the IDAT framing
+    with its CRC and IEND.
+    Out of scope: palette and sub-8-bit output, 16 bits, interlacing, ancillary chunks, matches across the 32 KiB chunks, Pillow's
+    `optimize` and `compress_level`."""
+    x4 = _png_encode_input("to_png", x)
+    b, h, w, c = x4.shape
+    if b == 0:
+        return []
+    with torch.cuda.device(x4.device):
+        plan = png_encode_plan(b, h, w, c)
+        raw = _png_filter(x4, plan)
+        sizes = torch.full((b,), plan["size"], dtype=torch.int64, device=x4.device)
+        out, lengths = _png_deflate(raw, sizes, plan["size"])
+        streams = _png_fetch(out, lengths, plan["size"] * _PNG_GUESS[0] // _PNG_GUESS[1] + 1024)
+    head = _PNG_SIGNATURE + _png_chunk(b"IHDR", w.to_bytes(4, "big") + h.to_bytes(4, "big") + bytes((8, _PNG_COLOUR_OF_CHANNELS[c], 0, 0, 0)))
+    tail = _png_chunk(b"IEND", b"")
+    files = [head + _png_chunk(b"IDAT", z) + tail for z in streams]
+    return files[0] if x.ndim == 3 else files
+
+
+def save_png(x, fp, nrow=8, padding=2, value_range=(-1, 1), pad_value=0.0):
+    """`torchvision.utils.save_image(x, "name.png", nrow=, padding=, normalize=True, range=value_range, pad_value=)` (0.8.2): fp32
+    [B,C,H,W] (C = 1 or 3) on the GPU -> to_bytes' canvas -> to_png -> the file.  fp: a path ending in .png, or an object with write().
+    The decoded file is the canvas exactly; see `to_png` for what is in and out of scope."""
+    if isinstance(fp, (str, os.PathLike)):
+        if os.path.splitext(os.fspath(fp))[1].lower() != ".png":
+            raise ValueError(f"save_png: {os.fspath(fp)!r} does not end in .png (JPEG goes through save_image)")
+    elif not hasattr(fp, "write"):
+        raise ValueError(f"save_png: fp is a path ending in .png or an object with write() (got {type(fp).__name__})")
+    data = to_png(to_bytes(x, value_range=value_range, nrow=nrow, padding=padding, pad_value=pad_value, grid=True))
+    if hasattr(fp, "write"):
+        fp.write(data)
+    else:
+        with open(fp, "wb") as f:
+            f.write(data)
 
 
 def clear_caches():
