@@ -60,7 +60,9 @@ extern "C" {
  * JPEG decoding, Pillow's pixels).
  * Still 7, additive: w2e_png_plan / w2e_png_inflate / w2e_png_pixels (w2e_png.h: PNG decoding, Pillow's pixels).
  * Still 7, additive: w2e_png_encode_plan / w2e_png_deflate_plan / w2e_png_filter / w2e_png_deflate (w2e_png.h: PNG encoding, Pillow's
- * filtered rows, the library's own chunked deflate). */
+ * filtered rows, the library's own chunked deflate).
+ * Still 7, additive: w2e_conv2d_bn_relu / w2e_pool3x3 / w2e_inception_resize (w2e_inception.h: the Inception-v3 feature extractor of
+ * the FID / Inception Score evaluation). */
 #define W2E_VERSION 7
 
 int w2e_version(void);

@@ -10,7 +10,11 @@ streaming kernel (`w2e_mask_iou_counts`: binarisation, label remap and the three
 
 Callers bring the dataset: `(image or W+ latent, parsing label already resized to the mask's S x S)` pairs, and the CLIP text
 features of the prompts (there is no tokeniser in this package).  Decoded bytes are welcome too: uint8 [B,H,W,3] images and, with
-`calculate_iou(label_resize=...)`, uint8 labels of any size are resized on the device with Pillow's own arithmetic (image_io.py)."""
+`calculate_iou(label_resize=...)`, uint8 labels of any size are resized on the device with Pillow's own arithmetic (image_io.py).
+
+Second half: the quality metrics of edits, `cal_evaluation` / `generate_imgs` (utils.py:434-551) -- Inception Score, FID, identity
+similarity and the share of edits whose CLIP score improves: `calculate_metrics`, `EditMetrics`, `fid_from_features`,
+`isc_from_logits`, on inception.FeatureExtractorInceptionV3."""
 import ctypes
 
 import torch
@@ -260,3 +264,188 @@ def celebamask_samples(img_dir, label_dir, batch=8, device=None):
         if labels.ndim != 3:
             raise ValueError(f"celebamask_samples: the labels {first}.png .. are no grey or palette files (decoded shape {tuple(labels.shape)})")
         yield images, labels
+
+
+# ---------------------------------------------------------------------------------------------- FID / Inception Score
+# utils.py:434-551 (cal_evaluation / generate_imgs): the reference writes the original and the edited images as quality-75 JPEG files
+# and hands the two directories to torch_fidelity.calculate_metrics(isc=True, fid=True).  The feature extractor is
+# inception.FeatureExtractorInceptionV3 on its HIP kernels; the two statistics below are float64 torch compositions over [N,2048] /
+# [N,1008] matrices -- plumbing, computed on the host (no dependence on the ROCm build's eigh).
+def _feature_matrix(f, what):
+    f = torch.as_tensor(f).detach().to("cpu", torch.float64)
+    if f.dim() != 2 or f.shape[0] < 2:
+        raise ValueError(f"{what}: features are [N,D] with N >= 2 (got {tuple(f.shape)})")
+    return f
+
+
+def feature_statistics(f):
+    """(mean [D], covariance [D,D] with N - 1) of features [N,D], float64."""
+    f = _feature_matrix(f, "feature_statistics")
+    mu = f.mean(0)
+    d = f - mu
+    return mu, d.T @ d / (f.shape[0] - 1)
+
+
+def fid_from_statistics(mu1, s1, mu2, s2):
+    """|mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr (S1 S2)^1/2.  The trace comes from eigenvalues, without a matrix square root of the
+    unsymmetric product: with R = S1^1/2 (eigh, eigenvalues clamped at 0) the matrices S1 S2 and R S2 R share their spectrum and the
+    latter is symmetric positive semi-definite, so tr (S1 S2)^1/2 = sum sqrt(eigvalsh(R S2 R)), clamped at 0.
+    R S2 R is formed in S1's eigenbasis, on the eigenvectors above S1's numerical rank tolerance (D eps lambda_max, matrix_rank's)
+    only: the rest contribute exactly 0 to R, but as rows and columns of rounding noise of size eps they would each add sqrt(eps) to
+    the trace -- with fewer samples than dimensions that is most of them, and a set's distance to itself would not be 0."""
+    mu1, s1, mu2, s2 = (torch.as_tensor(t).to("cpu", torch.float64) for t in (mu1, s1, mu2, s2))
+    lam, q = torch.linalg.eigh(s1)
+    keep = lam > lam.max().clamp_min(0) * lam.numel() * torch.finfo(torch.float64).eps
+    h = q[:, keep] * lam[keep].sqrt()  # R = h q_keep^T, so R S2 R = q_keep (h^T S2 h) q_keep^T: the same non-zero spectrum
+    m = h.T @ s2 @ h
+    tr = torch.linalg.eigvalsh((m + m.T) / 2).clamp_min(0).sqrt().sum()
+    diff = mu1 - mu2
+    return float(diff @ diff + torch.trace(s1) + torch.trace(s2) - 2 * tr)
+
+
+def fid_from_features(f1, f2):
+    """The Frechet distance of two feature sets [N1,D], [N2,D] (torch_fidelity's frechet_inception_distance on the '2048' features)."""
+    return fid_from_statistics(*feature_statistics(f1), *feature_statistics(f2))
+
+
+def isc_from_logits(logits, splits=10, shuffle=True, rng_seed=2020):
+    """torch_fidelity's Inception Score of the UNBIASED logits [N,1008]: (mean, population standard deviation) over `splits` of
+    exp(mean_i sum_c p_ic (log p_ic - log mean_i p_ic)); the rows are first permuted by numpy.random.RandomState(rng_seed), split k
+    holds rows [k N // splits, (k + 1) N // splits).  float64."""
+    import numpy as np
+    x = torch.as_tensor(logits).detach().to("cpu", torch.float64)
+    if x.dim() != 2 or not 1 <= splits <= x.shape[0]:
+        raise ValueError(f"isc_from_logits: logits are [N,C] with N >= splits >= 1 (got {tuple(x.shape)}, splits {splits})")
+    n = x.shape[0]
+    if shuffle:
+        x = x[torch.from_numpy(np.random.RandomState(rng_seed).permutation(n))]
+    logp = torch.log_softmax(x, dim=1)
+    scores = []
+    for k in range(splits):
+        lp = logp[k * n // splits:(k + 1) * n // splits]
+        p = lp.exp()
+        log_marginal = p.mean(0, keepdim=True).log()
+        scores.append((p * (lp - log_marginal)).sum(1).mean().exp())
+    scores = torch.stack(scores)
+    return float(scores.mean()), float(scores.std(unbiased=False))
+
+
+_IMAGE_SUFFIXES = (".jpg", ".jpeg", ".png")
+
+
+def _image_batches(source, batch, device):
+    """uint8 [b,H,W,3] batches on the GPU of one `calculate_metrics` input: a uint8 tensor [N,H,W,3] (or [H,W,3]), a list of such
+    tensors, or a directory of .jpg / .png files (sorted by name, decoded by image_io.read_image, grouped by size)."""
+    import os
+    if isinstance(source, (str, os.PathLike)):
+        from .image_io import read_image
+        names = sorted(n for n in os.listdir(source) if os.path.splitext(n)[1].lower() in _IMAGE_SUFFIXES)
+        if not names:
+            raise ValueError(f"calculate_metrics: no .jpg / .png file in {os.fspath(source)!r}")
+        source = [read_image(os.path.join(source, n), device=device) for n in names]
+    if torch.is_tensor(source):
+        source = [source]
+    groups = {}
+    for t in source:
+        if not (torch.is_tensor(t) and t.dtype == torch.uint8 and t.dim() in (3, 4) and t.shape[-1] == 3):
+            raise ValueError("calculate_metrics: an input is a uint8 tensor [N,H,W,3], a list of uint8 [H,W,3] / [N,H,W,3] tensors, or a directory "
+                             f"(got {type(t).__name__}{'' if not torch.is_tensor(t) else f' {t.dtype} {tuple(t.shape)}'})")
+        t = t[None] if t.dim() == 3 else t
+        groups.setdefault(tuple(t.shape[1:3]), []).append(t)
+    for members in groups.values():
+        images = members[0] if len(members) == 1 else torch.cat(members)
+        for first in range(0, images.shape[0], batch):
+            yield images[first:first + batch].to(device)
+
+
+def inception_features(source, extractor, batch=32, features=("2048", "logits_unbiased")):
+    """The named features of every image of `source` (see `_image_batches`), each [N,D] on the extractor's device."""
+    device = next(extractor.parameters()).device
+    chunks = [[] for _ in features]
+    with torch.cuda.device(device):
+        for images in _image_batches(source, batch, device):
+            for acc, f in zip(chunks, extractor(images, features=features)):
+                acc.append(f)
+    return tuple(torch.cat(c) for c in chunks)
+
+
+def calculate_metrics(input1, input2, isc=True, fid=True, batch=32, extractor=None, isc_splits=10):
+    """torch_fidelity.calculate_metrics(input1, input2, isc=, fid=) (utils.py:545-550): the Inception Score of input1 and the Frechet
+    Inception Distance between the two inputs, under torch_fidelity's keys.  Each input: a uint8 [N,H,W,3] tensor, a list of uint8
+    tensors, or a directory of .jpg / .png files (read on the GPU, grouped by size into batches of at most `batch`).  extractor: a
+    FeatureExtractorInceptionV3 on the GPU with the pretrained weights loaded; None builds one with its seeded random weights, whose
+    numbers are comparable only with each other.  isc_splits: torch_fidelity's keyword of that name (input1 needs that many images)."""
+    if extractor is None:
+        from .inception import FeatureExtractorInceptionV3
+        extractor = FeatureExtractorInceptionV3().to("cuda")
+    if not (isinstance(batch, int) and batch >= 1):
+        raise ValueError(f"calculate_metrics: batch is a positive integer (got {batch!r})")
+    out = {}
+    f1, l1 = inception_features(input1, extractor, batch)
+    if isc:
+        out["inception_score_mean"], out["inception_score_std"] = isc_from_logits(l1, splits=isc_splits)
+    if fid:
+        (f2,) = inception_features(input2, extractor, batch, features=("2048",))
+        out["frechet_inception_distance"] = fid_from_features(f1, f2)
+    return out
+
+
+class EditMetrics:
+    """`generate_imgs` + `cal_evaluation` (utils.py:434-551) over tensors.  `update(img_orig, img_gen, text_features)` takes the
+    generator's fp32 images [B,3,H,W] in [-1, 1]; `compute()` returns (IS of the edited images, FID original vs edited, mean identity
+    similarity, share of edits whose CLIP score against the text improved), as cal_evaluation does.
+    jpeg=True: each image goes through to_bytes(grid=False) -> to_jpeg -> from_jpeg first -- the reference's metric reads the
+    quality-75 JPEG files save_image wrote; this is that round trip without the disk.  jpeg=False feeds to_bytes' pixels directly.
+    id_loss(img_gen, img_orig) -> (loss, ...) as criteria/id_loss.py: (1 - loss) * B is accumulated.  clip_loss: an object with
+    `preprocess(images)` and `encode_image(images)` (CLIPLoss): an edit improves when cos(clip(gen), text) > cos(clip(orig), text).
+    Either may be None; its entry of the result is then None.  isc_splits: the splits of the Inception Score (torch_fidelity's 10)."""
+
+    def __init__(self, extractor, clip_loss=None, id_loss=None, jpeg=True, isc_splits=10):
+        self.extractor, self.clip_loss, self.id_loss, self.jpeg, self.isc_splits = extractor, clip_loss, id_loss, bool(jpeg), int(isc_splits)
+        self.reset()
+
+    def reset(self):
+        self._f_orig, self._f_gen, self._logits = [], [], []
+        self._id, self._improved, self._count = None, None, 0
+
+    def _pixels(self, img):
+        from .image_io import from_jpeg, to_bytes, to_jpeg
+        u8 = to_bytes(img.detach().float(), grid=False)
+        if self.jpeg:
+            u8 = from_jpeg(to_jpeg(u8), device=img.device, stack=True)
+        return u8
+
+    @torch.no_grad()
+    def update(self, img_orig, img_gen, text_features=None):
+        if img_orig.shape != img_gen.shape or img_orig.dim() != 4 or img_orig.shape[1] != 3:
+            raise ValueError(f"EditMetrics.update: images are two [B,3,H,W] tensors of one shape (got {tuple(img_orig.shape)}, {tuple(img_gen.shape)})")
+        b = img_orig.shape[0]
+        with torch.cuda.device(img_orig.device):
+            (f_orig,) = self.extractor(self._pixels(img_orig), features=("2048",))
+            f_gen, logits = self.extractor(self._pixels(img_gen), features=("2048", "logits_unbiased"))
+            self._f_orig.append(f_orig), self._f_gen.append(f_gen), self._logits.append(logits)
+            if self.id_loss is not None:
+                term = (1 - torch.as_tensor(self.id_loss(img_gen, img_orig)[0], device=img_orig.device).float()) * b
+                self._id = term if self._id is None else self._id + term
+            if self.clip_loss is not None:
+                if text_features is None:
+                    raise ValueError("EditMetrics.update: clip_loss needs the CLIP text features of the prompt")
+                text = text_features.float()
+                text = text / text.norm(dim=-1, keepdim=True)
+                score = []
+                for img in (img_gen, img_orig):
+                    e = self.clip_loss.encode_image(self.clip_loss.preprocess(img)).float()
+                    score.append(((e / e.norm(dim=-1, keepdim=True)) * text).sum(-1))
+                better = (score[0] > score[1]).sum()
+                self._improved = better if self._improved is None else self._improved + better
+        self._count += b
+
+    def compute(self):
+        """(IS, FID, ID, improve).  The first host synchronisation of the evaluation."""
+        if self._count < 2:
+            raise RuntimeError("EditMetrics.compute: fewer than two images were added")
+        inception = isc_from_logits(torch.cat(self._logits), splits=self.isc_splits)[0]
+        fid = fid_from_features(torch.cat(self._f_orig), torch.cat(self._f_gen))
+        ident = None if self._id is None else float(self._id) / self._count
+        improve = None if self._improved is None else float(self._improved) / self._count
+        return inception, fid, ident, improve
