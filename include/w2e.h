@@ -62,7 +62,8 @@ extern "C" {
  * Still 7, additive: w2e_png_encode_plan / w2e_png_deflate_plan / w2e_png_filter / w2e_png_deflate (w2e_png.h: PNG encoding, Pillow's
  * filtered rows, the library's own chunked deflate).
  * Still 7, additive: w2e_conv2d_bn_relu / w2e_pool3x3 / w2e_inception_resize (w2e_inception.h: the Inception-v3 feature extractor of
- * the FID / Inception Score evaluation). */
+ * the FID / Inception Score evaluation).
+ * Still 7, additive: w2e_lpips_head_fwd / w2e_lpips_head_bwd (w2e_lpips.h: the five-tap head of LPIPS-VGG v0.1 and its adjoint). */
 #define W2E_VERSION 7
 
 int w2e_version(void);

@@ -22,6 +22,7 @@ Layout:
   evaluation.py           the region mask's IoU against parsing labels (utils.py:639-726): MaskIoU, calculate_iou; FID / Inception Score /
                           identity / CLIP-improvement of edits (utils.py:434-551): calculate_metrics, EditMetrics
   inception.py            the Inception-v3 feature extractor of FID / IS on csrc/inception.hip: FeatureExtractorInceptionV3
+  lpips.py                LPIPS (VGG16, v0.1) on the VGG16 kernels and the head of csrc/lpips.hip: LPIPS; evaluation.lpips_distance
   image_io.py             bytes in, bytes out on csrc/image.hip: Pillow's resize + ToTensor / Normalize (to_tensor, label_ids, resize_u8),
                           torchvision's save_image up to the PNG encoder (to_bytes), its .jpg file (to_jpeg, save_image), and
                           baseline JPEG files in (from_jpeg, load_image) on csrc/jpeg.hip and csrc/jpeg_decode.hip, PNG files in
@@ -65,7 +66,7 @@ def r1_penalty(discriminator, real, return_logits=False):
 
 # where2edit_amd.evaluation's public names, importable from the package (resolved on first use: importing the package stays light)
 _EVALUATION = ("CELEBAMASK_REGIONS", "region_lut", "binarise", "attention_with_text", "MaskIoU", "calculate_iou", "celebamask_samples",
-               "fid_from_features", "isc_from_logits", "calculate_metrics", "EditMetrics")
+               "fid_from_features", "isc_from_logits", "calculate_metrics", "EditMetrics", "lpips_distance")
 _IMAGE_IO = ("resample_tables", "resize_u8", "to_tensor", "label_ids", "to_bytes", "jpeg_tables", "jpeg_header", "jpeg_coefficients", "to_jpeg",
              "save_image", "jpeg_parse", "jpeg_decode_states", "jpeg_decode_coefficients", "jpeg_pixels", "from_jpeg", "load_image",
              "png_parse", "png_plan", "png_inflate", "png_pixels", "from_png", "load_png", "read_image", "png_encode_plan", "png_filter", "png_deflate",
@@ -79,6 +80,9 @@ def __getattr__(name):
     if name == "FeatureExtractorInceptionV3":  # the FID / Inception Score network on csrc/inception.hip (inception.py)
         from .inception import FeatureExtractorInceptionV3
         return FeatureExtractorInceptionV3
+    if name == "LPIPS":  # the perceptual metric: VGG16 on the conv engine, the head on csrc/lpips.hip (lpips.py)
+        from .lpips import LPIPS
+        return LPIPS
     if name in _EVALUATION:
         from . import evaluation
         return getattr(evaluation, name)

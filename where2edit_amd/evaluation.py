@@ -390,6 +390,65 @@ def calculate_metrics(input1, input2, isc=True, fid=True, batch=32, extractor=No
     return out
 
 
+def _images_in_order(source, device, what):
+    """The images of one `lpips_distance` input as a list of uint8 [H,W,3] tensors, in order: a uint8 tensor [N,H,W,3] (or [H,W,3]),
+    a list of such tensors, or a directory of .jpg / .png files (sorted by name, decoded by image_io.read_image on `device`)."""
+    import os
+    if isinstance(source, (str, os.PathLike)):
+        from .image_io import read_image
+        names = sorted(n for n in os.listdir(source) if os.path.splitext(n)[1].lower() in _IMAGE_SUFFIXES)
+        if not names:
+            raise ValueError(f"lpips_distance: no .jpg / .png file in {os.fspath(source)!r}")
+        source = [read_image(os.path.join(source, n), device=device) for n in names]
+    if torch.is_tensor(source):
+        source = [source]
+    images = []
+    for t in source:
+        if not (torch.is_tensor(t) and t.dtype == torch.uint8 and t.dim() in (3, 4) and t.shape[-1] == 3):
+            raise ValueError(f"lpips_distance: {what} is a uint8 tensor [N,H,W,3], a list of uint8 [H,W,3] / [N,H,W,3] tensors, or a directory "
+                             f"(got {type(t).__name__}{'' if not torch.is_tensor(t) else f' {t.dtype} {tuple(t.shape)}'})")
+        images += [t] if t.dim() == 3 else list(t.unbind(0))
+    return images
+
+
+@torch.no_grad()
+def lpips_distance(input1, input2, model=None, batch=32):
+    """LPIPS of paired images -- original against edit: how much changed.  input1 / input2: what `calculate_metrics` takes (a uint8
+    [N,H,W,3] tensor, a list of uint8 tensors, or a directory of .jpg / .png files read on the GPU); image i of input1 is paired with
+    image i of input2, so the counts must agree and so must the two sizes of every pair.  The bytes become [-1, 1] tensors through
+    image_io.to_tensor (no resize) and go through `model` in batches of at most `batch` consecutive pairs of one size.
+    Returns {"lpips_mean": float, "lpips": fp32 tensor [N] on the model's device}; the float is the one host synchronisation.
+    model: an lpips.LPIPS on the GPU with the published weights loaded.  None builds one with its SEEDED RANDOM weights: such numbers
+    rank edits of one run against each other and are no LPIPS of the literature (lpips.py says what to load)."""
+    if not (isinstance(batch, int) and batch >= 1):
+        raise ValueError(f"lpips_distance: batch is a positive integer (got {batch!r})")
+    device = torch.device("cuda") if model is None or not hasattr(model, "parameters") else next(model.parameters()).device
+    first, second = _images_in_order(input1, device, "input1"), _images_in_order(input2, device, "input2")
+    if len(first) != len(second):
+        raise ValueError(f"lpips_distance: input1 holds {len(first)} images, input2 {len(second)}: pairs are by order, the counts must agree")
+    for i, (a, b) in enumerate(zip(first, second)):
+        if a.shape != b.shape:
+            raise ValueError(f"lpips_distance: pair {i} has sizes {tuple(a.shape[:2])} and {tuple(b.shape[:2])}: resize one side first")
+    if not first:
+        raise ValueError("lpips_distance: no images")
+    if model is None:
+        from .lpips import LPIPS
+        model = LPIPS().to(device)
+    from .image_io import to_tensor
+    out, i = [], 0
+    with torch.cuda.device(device):
+        while i < len(first):
+            j = i + 1
+            while j < len(first) and j - i < batch and first[j].shape == first[i].shape:
+                j += 1
+            x0 = to_tensor(torch.stack(first[i:j]).to(device))
+            x1 = to_tensor(torch.stack(second[i:j]).to(device))
+            out.append(model(x0, x1).reshape(-1))
+            i = j
+    d = torch.cat(out)
+    return {"lpips_mean": float(d.mean()), "lpips": d}
+
+
 class EditMetrics:
     """`generate_imgs` + `cal_evaluation` (utils.py:434-551) over tensors.  `update(img_orig, img_gen, text_features)` takes the
     generator's fp32 images [B,3,H,W] in [-1, 1]; `compute()` returns (IS of the edited images, FID original vs edited, mean identity
