@@ -9,7 +9,11 @@ Bound, for EVERY output element:  |got - ref| <= gamma * sum|terms|,  gamma = (K
 correct fp32 sum of K products, with a few roundings for scale, bias and activation (a dropped or doubled term of typical size lands
 near 1/K of sum|terms|, about 60 times above).  sum|terms| is the same formula in float64 on |a|, |W|, |bias|, times the slope the
 reference took (lrelu is 1-Lipschitz times its gain, so an element whose pre-activation is within the bound of 0 is judged with
-slope 1).  Outputs are pre-filled with NaN between sentinels that must survive.  `-s` prints the worst ratio of every case."""
+slope 1).  Outputs are pre-filled with NaN between sentinels that must survive.  `-s` prints the worst ratio of every case.
+
+The other entry points of csrc/mapper.hip -- w2e_mapper_pixelnorm, w2e_mapper_wgrad and the style-space w2e_ssmapper_* -- are held the
+same way by tests/test_gpu_mapper_rest_kernels.py, which runs CASES too and holds a census of what the mappers really call against
+both files (its COVERAGE table states this file's path classes: mode 0 x scatter x bias given / NULL, mode 1 x gathered, 1-4 groups)."""
 import math
 
 import pytest
@@ -31,6 +35,7 @@ CASES = {
     "step_b4": (4, STEP_LEVELS),                            # the step's own shape: 16 / 16 / 40 rows
     "b1": (1, STEP_LEVELS),                                 # 4 / 4 / 10 rows: fewer rows than any tile
     "b3_medium_only": (3, ((4, 4),)),                       # a disabled level: uncovered latents of the scattered output stay 0
+    "b3_no_medium": (3, ((0, 4), (8, 10))),                 # LevelsMapper with no_medium_mapper: two groups, 12 / 30 rows, a gap between them
     "b5_single": (5, ((0, 18),)),                           # 90 rows: no multiple of 16 or 32
     "b64_single": (64, ((0, 18),)),                         # 1152 rows = MAP_MAXROWS
     "b2_four_groups": (2, ((0, 1), (1, 2), (3, 5), (8, 10))),  # four groups, one with 2 rows
