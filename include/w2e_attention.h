@@ -43,7 +43,8 @@ int w2e_cluster_accumulate(const float* feat, const int32_t* assign, float* part
  * One persistent kernel in three modes over the same points ([B,C,S,S] + the 2P analytic position channels), a grid of
  * `grid` workgroups (w2e_kmeans_plan) walking 128-pixel tiles, each writing one row of `partial` (written, not accumulated):
  *   mode 0  assignment:  assign[b,y,x] exactly as w2e_cluster_assign (bit-identical distances), mind[b,y,x] = the squared distance
- *           to that centre (assign / mind may be NULL); partial [grid][1] = the workgroup's share of the inertia.
+ *           to that centre (assign / mind may be NULL); partial [grid][1] = the workgroup's share of the inertia.  Takes every
+ *           shape w2e_cluster_assign takes (up to D = 1024 at K = 32).
  *   mode 1  fused Lloyd step: mode 0 plus the per-cluster sums and counts of the tile, taken while it is still in cache;
  *           partial [grid][K*(D+1) + 1]: [k][d] sums (d < D = C+2P), [k][D] the count, then the inertia share.  Needs an even S
  *           and centres + sums within the 160 KB of LDS (w2e_kmeans_plan reports `fused` = 0 otherwise: run mode 0 and

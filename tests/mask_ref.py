@@ -72,7 +72,7 @@ ASSIGN_SHAPES = [
     (3, 0, 5, 1, 2),       # wave 0 owns no channel; P = 0; K = 1
     (16, 1, 64, 32, 1),    # full K = 32
     (16, 1, 2, 17, 1),     # minimum S = 2
-    (960, 32, 8, 32, 1),   # exactly the 160 KB bound
+    (960, 32, 8, 32, 1),   # exactly the 160 KB bound of cluster_assign (in w2e_kmeans_pass mode 0: the three-block kernel; KMEANS_WIDE_SHAPES)
 ]
 ASSIGN_GAP = 1e-4       # a pixel whose float64 runner-up is closer than this (relative) may go either way
 ASSIGN_SLACK = 1e-5     # the chosen centre is at most this much (relative) farther than the float64 minimum
@@ -131,6 +131,102 @@ def tie_case():
     feat = torch.from_numpy(rs.randint(-2, 3, size=(2, 6, 9, 9)).astype(np.float32))
     feat[0, :, 0, 0] = 0.0  # a pixel at the origin: ties with the zero padding unless k < K is honoured
     return feat.contiguous(), cen.contiguous()
+
+
+# ---------------------------------------------------------------------------------------------------- the k-means pass kernel
+# The shapes (C, P, S, K, B) at which the fused Lloyd step of csrc/kmeans.hip (w2e_kmeans_pass mode 1) is tested: even S, centres + sums
+# within the LDS.  The kernel walks 128-pixel tiles, eight waves = 2 pixel halves x 4 channel quarters, 16 planes in flight.
+KMEANS_STEP_SHAPES = [
+    (512, 32, 16, 20, 2),  # KP = 24; D = 576 > 512: a thread of the second read owns columns t and t + 512; 2 full tiles per image
+    (37, 2, 10, 8, 3),     # quarters 9/9/9/10; prefetch tail; 100 pixels per image: one partial tile, 36 live lanes in the upper half; K = KP
+    (64, 4, 14, 9, 1),     # KP = 16; 196 pixels: the second tile has 68 live pixels, 4 live lanes in the upper half
+    (3, 0, 6, 1, 2),       # a wave with no channel; P = 0; K = 1; 36 pixels: an upper half with no live lane
+    (16, 1, 64, 32, 1),    # 32 full tiles
+    (16, 1, 2, 17, 1),     # 4 pixels
+    (18, 1, 12, 5, 5),     # C % 4 != 0 (quarters 4/5/4/5); 144 pixels: the second tile has 16 live pixels; 10 tiles: at grid 3 a workgroup
+                           # takes tiles of different images
+]
+# Assignment and seeding modes: every shape of w2e_cluster_assign's test, then the step's
+KMEANS_SHAPES = ASSIGN_SHAPES + [shape for shape in KMEANS_STEP_SHAPES if shape not in ASSIGN_SHAPES]
+# Mode 0 beside centres that leave no room for six [64][KP] blocks of partial distances (160 KB = 40960 floats; the kernel needs
+# D * KP + blocks * 64 * KP + 128 + 2 * KP): its three-block instantiations of KP = 8, 16 and 32, in which the two pixel halves of a
+# tile take turns at the blocks.  (960, 32, 8, 32, 1) above is a KP = 32 case too, but its 64 pixels leave the upper half without a
+# live lane and give no workgroup a second tile.  S = 14, B = 2: 196 pixels per image, a full tile and one of 68 pixels (4 live lanes in
+# the upper half), 4 tiles, so that at grid 1 and 3 a workgroup reuses the blocks from tile to tile.  All three are shapes that
+# w2e_cluster_assign takes.  (KP = 24 has no three-block form: (1400, 0, ., 20, .) is refused.)
+KMEANS_WIDE_SHAPES = [
+    (4800, 0, 14, 5, 2),    # KP = 8:  41616 floats with six blocks, 40080 with three
+    (2200, 0, 14, 12, 2),   # KP = 16: 41504 / 38432
+    (960, 32, 14, 32, 2),   # KP = 32: 45248 / 39104
+]
+KMEANS_TILE = 128
+KMEANS_SEED_CANDIDATES = (1, 3, 8)
+
+
+def kmeans_tiles(s, b):
+    """(tiles per image, tiles, live pixels of an image's last tile)"""
+    per = -(-s * s // KMEANS_TILE)
+    return per, b * per, s * s - (per - 1) * KMEANS_TILE
+
+
+def kmeans_kp(k):
+    return 8 if k <= 8 else 16 if k <= 16 else 24 if k <= 24 else 32
+
+
+def kmeans_step_fits(c, p, s, k):
+    """include/w2e_attention.h, mode 1: an even S, and centres [D][KP] + six blocks of partial distances [64][KP] + the tile's ids [128] +
+    [2][KP] + the running sums and counts [K][D+1], in floats, within 160 KB of LDS."""
+    d, kp = c + 2 * p, kmeans_kp(k)
+    return s % 2 == 0 and 4 * (d * kp + 6 * 64 * kp + KMEANS_TILE + 2 * kp + k * (d + 1)) <= 160 * 1024
+
+
+def kmeans_step_run(s):
+    """(length of the single-id run, length of the alternating stretch after it) of kmeans_step_labelling"""
+    run = 130 if s * s > KMEANS_TILE else s * s // 2
+    return run, min(32, s * s - run)
+
+
+def kmeans_step_labelling(s, k, b):
+    """Ids [B,S,S] for the fused step's run-length flush, per image in pixel order: one run of a single id (130 pixels -- longer than a
+    tile -- where the image has more than a tile, else half the image), then 32 pixels (or what is left) that alternate between two ids,
+    then seeded ids.  Cluster K - 1 is never used (K = 1: all 0; K = 2: one usable id, so no alternation)."""
+    npix, usable = s * s, max(k - 1, 1)
+    run, alt = kmeans_step_run(s)
+    rs = np.random.RandomState(s * 1000 + k * 10 + b + 1)
+    lab = rs.randint(0, usable, size=(b, npix))
+    for bb in range(b):
+        lab[bb, :run] = bb % usable
+        lab[bb, run:run + alt] = (np.arange(alt) + bb) % 2 % usable + (usable > 2)  # ids 1, 2 (or 0, 1 of two usable ids)
+    return torch.from_numpy(lab.reshape(b, s, s))
+
+
+def kmeans_step_case(c, p, s, k, b):
+    """assign_case with the labelling of kmeans_step_labelling, and centre K - 1 moved far away from every point (+100 in every feature
+    channel): an empty cluster.  (feat [B,C,S,S], centroids [K, C+2P], the labelling [B,S,S])"""
+    key = f"maskk.kmeans.step.{c}.{p}.{s}.{k}.{b}"
+    protos = seeded.tensor(key + ".protos", (k, c), 1.0)
+    lab = kmeans_step_labelling(s, k, b)
+    feat = (protos[lab].permute(0, 3, 1, 2) + 0.25 * seeded.tensor(key + ".noise", (b, c, s, s))).contiguous()
+    cen = torch.cat([protos, 0.05 * seeded.tensor(key + ".cpos", (k, 2 * p))], 1).contiguous()
+    if k > 1:
+        cen[k - 1, :c] += 100.0
+    return feat, cen, lab
+
+
+def longest_run(ids):
+    """Length of the longest stretch of equal consecutive entries of a 1-D tensor."""
+    change = torch.nonzero(ids[1:] != ids[:-1]).reshape(-1) + 1
+    edges = torch.cat([torch.zeros(1, dtype=torch.long), change, torch.tensor([ids.numel()])])
+    return int((edges[1:] - edges[:-1]).max())
+
+
+def longest_alternation(ids):
+    """Length of the longest stretch of a 1-D tensor in which every entry differs from the one before it."""
+    best = cur = 1
+    for changed in (ids[1:] != ids[:-1]).tolist():
+        cur = cur + 1 if changed else 1
+        best = max(best, cur)
+    return best
 
 
 # ---------------------------------------------------------------------------------------------------- demodulation, logits

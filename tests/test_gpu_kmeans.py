@@ -117,7 +117,9 @@ def test_ten_seeded_starts_always_reach_the_optimum_single_forgy_runs_do_not():
 
 def test_training_time_shape_times_eight():
     """[8,512,64,64] random activations, K = 20: predict is cluster_assign bit for bit (same distance arithmetic), and the fused
-    step's sums are cluster_sums' on that assignment."""
+    step's sums are cluster_sums' on that assignment.  256 full tiles: on 256 CUs w2e_kmeans_plan gives every workgroup exactly one,
+    as it does on the [4,64,32,32] fixture above (32 tiles).  Workgroups that walk several tiles, partial tiles, the KP = 16 kernels
+    and the other shapes at which the pass kernel takes another path are in tests/test_gpu_kmeans_kernels.py, which chooses the grid."""
     from where2edit_amd import clustering_feature as CF
     from where2edit_amd.run_attention import cluster_assign
     pts = seeded.tensor("kmeans_scale.points", (8, 512, 64, 64)).to(DEV)

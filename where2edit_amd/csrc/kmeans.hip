@@ -28,20 +28,23 @@ constexpr int KM_FLY = 16;       // channel planes in flight per wave
 
 enum { KM_ASSIGN = 0, KM_STEP = 1, KM_SEED = 2 };
 
-__host__ __device__ inline int64_t km_lds_floats(int D, int KP, int K, int mode) {
-    return (int64_t)D * KP + 6 * 64 * KP + KM_TILE + 2 * KP + (mode == KM_STEP ? (int64_t)K * (D + 1) : 0);
+__host__ __device__ inline int64_t km_lds_floats(int D, int KP, int K, int mode, int slots = 6) {
+    return (int64_t)D * KP + (int64_t)slots * 64 * KP + KM_TILE + 2 * KP + (mode == KM_STEP ? (int64_t)K * (D + 1) : 0);
 }
 
-template <int KP, int MODE>
+// SLOTS: blocks of [64][KP] partial distances.  6: one per (half, quarter 1..3), the halves join at once.  3, for centres that leave no
+// room for six (mode 0 only: D = 1024 at K = 32 is 128 KB of centres): the halves take turns at the same three blocks, at two more
+// barriers per tile; the additions and their order are the same, so is every bit of the result.
+template <int KP, int MODE, int SLOTS = 6>
 __global__ __launch_bounds__(KM_THREADS) void kmeans_pass_kernel(const float* __restrict__ feat, const float* __restrict__ cen,
                                                                  int32_t* __restrict__ assign, float* __restrict__ mind,
                                                                  float* __restrict__ candd, int64_t cand_ld,
                                                                  float* __restrict__ partial, int C, int P, int S, int K,
                                                                  int n_tiles, int tiles_per_img) {
-    extern __shared__ float lds[];  // [D][KP] centres | [6][64][KP] partial distances | [128] tile assignment | [2][KP] | [K][D+1] sums
+    extern __shared__ float lds[];  // [D][KP] centres | [SLOTS][64][KP] partial distances | [128] tile assignment | [2][KP] | [K][D+1] sums
     const int D = C + 2 * P, D1 = D + 1, npix = S * S;
     float* part = lds + D * KP;
-    int* tk = reinterpret_cast<int*>(part + 6 * 64 * KP);
+    int* tk = reinterpret_cast<int*>(part + SLOTS * 64 * KP);
     float* red = reinterpret_cast<float*>(tk + KM_TILE);
     float* sums = red + 2 * KP;
     for (int e = threadIdx.x; e < D * KP; e += KM_THREADS) {
@@ -99,45 +102,51 @@ __global__ __launch_bounds__(KM_THREADS) void kmeans_pass_kernel(const float* __
                 }
             }
         }
-        if (q != 0) {
-            float4* dst = reinterpret_cast<float4*>(part + ((half * 3 + q - 1) * 64 + lane) * KP);
+        constexpr int TURNS = SLOTS == 6 ? 1 : 2;
 #pragma unroll
-            for (int j = 0; j < KP / 4; ++j) dst[j] = make_float4(dist[4 * j], dist[4 * j + 1], dist[4 * j + 2], dist[4 * j + 3]);
-        }
-        __syncthreads();
-        if (q == 0) {
-            const float* p1 = part + ((half * 3 + 0) * 64 + lane) * KP;
-            const float* p2 = part + ((half * 3 + 1) * 64 + lane) * KP;
-            const float* p3 = part + ((half * 3 + 2) * 64 + lane) * KP;
+        for (int turn = 0; turn < TURNS; ++turn) {
+            const bool mine = SLOTS == 6 || half == turn;
+            const int blk = SLOTS == 6 ? half * 3 : 0;
+            if (q != 0 && mine) {
+                float4* dst = reinterpret_cast<float4*>(part + ((blk + q - 1) * 64 + lane) * KP);
 #pragma unroll
-            for (int k = 0; k < KP; ++k) dist[k] = ((dist[k] + p1[k]) + p2[k]) + p3[k];
-            if (MODE == KM_SEED) {
-                if (live) {
-                    const int64_t n = (int64_t)b * npix + pix;
-                    const float m = mind ? mind[n] : __builtin_inff();
-#pragma unroll
-                    for (int t = 0; t < KP; ++t)
-                        if (t < K) {
-                            candd[t * cand_ld + n] = dist[t];
-                            tot[t] += fminf(m, dist[t]);
-                        }
-                }
-            } else {
-                int best = 0;
-                float bd = dist[0];
-#pragma unroll
-                for (int k = 1; k < KP; ++k)
-                    if (k < K && dist[k] < bd) bd = dist[k], best = k;
-                if (live) {
-                    const int64_t n = (int64_t)b * npix + pix;
-                    if (assign) assign[n] = best;
-                    if (mind) mind[n] = bd;
-                    tot[0] += bd;
-                }
-                tk[half * 64 + lane] = live ? best : -1;
+                for (int j = 0; j < KP / 4; ++j) dst[j] = make_float4(dist[4 * j], dist[4 * j + 1], dist[4 * j + 2], dist[4 * j + 3]);
             }
+            __syncthreads();
+            if (q == 0 && mine) {
+                const float* p1 = part + ((blk + 0) * 64 + lane) * KP;
+                const float* p2 = part + ((blk + 1) * 64 + lane) * KP;
+                const float* p3 = part + ((blk + 2) * 64 + lane) * KP;
+#pragma unroll
+                for (int k = 0; k < KP; ++k) dist[k] = ((dist[k] + p1[k]) + p2[k]) + p3[k];
+                if (MODE == KM_SEED) {
+                    if (live) {
+                        const int64_t n = (int64_t)b * npix + pix;
+                        const float m = mind ? mind[n] : __builtin_inff();
+#pragma unroll
+                        for (int t = 0; t < KP; ++t)
+                            if (t < K) {
+                                candd[t * cand_ld + n] = dist[t];
+                                tot[t] += fminf(m, dist[t]);
+                            }
+                    }
+                } else {
+                    int best = 0;
+                    float bd = dist[0];
+#pragma unroll
+                    for (int k = 1; k < KP; ++k)
+                        if (k < K && dist[k] < bd) bd = dist[k], best = k;
+                    if (live) {
+                        const int64_t n = (int64_t)b * npix + pix;
+                        if (assign) assign[n] = best;
+                        if (mind) mind[n] = bd;
+                        tot[0] += bd;
+                    }
+                    tk[half * 64 + lane] = live ? best : -1;
+                }
+            }
+            __syncthreads();  // (also: `part` is free again before a faster wave writes the next tile's partials)
         }
-        __syncthreads();  // (also: `part` is free again before a faster wave writes the next tile's partials)
         if (MODE == KM_STEP) {
             for (int d = threadIdx.x; d <= D; d += KM_THREADS) {
                 const float* row = feat + ((int64_t)b * C + (d < C ? d : 0)) * npix + px0;
@@ -209,12 +218,12 @@ __global__ __launch_bounds__(256) void kmeans_reduce_kernel(const float* __restr
 
 inline int km_kp(int clusters) { return clusters <= 8 ? 8 : clusters <= 16 ? 16 : clusters <= 24 ? 24 : 32; }
 
-template <int KP, int MODE>
+template <int KP, int MODE, int SLOTS = 6>
 int km_launch(unsigned* done, size_t lds, int grid, hipStream_t s, const float* feat, const float* cen, int32_t* assign, float* mind,
               float* candd, int64_t cand_ld, float* partial, int C, int P, int S, int K, int n_tiles, int tiles_per_img) {
-    if (lds > 64 * 1024) W2E_REQUIRE(big_lds_once((const void*)kmeans_pass_kernel<KP, MODE>, done), "kmeans_pass: LDS opt-in failed");
-    kmeans_pass_kernel<KP, MODE><<<grid, KM_THREADS, lds, s>>>(feat, cen, assign, mind, candd, cand_ld, partial, C, P, S, K, n_tiles,
-                                                               tiles_per_img);
+    if (lds > 64 * 1024) W2E_REQUIRE(big_lds_once((const void*)kmeans_pass_kernel<KP, MODE, SLOTS>, done), "kmeans_pass: LDS opt-in failed");
+    kmeans_pass_kernel<KP, MODE, SLOTS><<<grid, KM_THREADS, lds, s>>>(feat, cen, assign, mind, candd, cand_ld, partial, C, P, S, K, n_tiles,
+                                                                      tiles_per_img);
     return 0;
 }
 
@@ -252,16 +261,25 @@ extern "C" int w2e_kmeans_pass(int mode, const float* feat, const float* centroi
     W2E_REQUIRE(tiles < (1ll << 31), "kmeans_pass: too many tiles");
     W2E_REQUIRE(grid >= 1 && grid <= 4096, "kmeans_pass: grid %d (w2e_kmeans_plan)", grid);
     const int KP = km_kp(clusters), D = channels + 2 * pos_channels;
-    const size_t lds = (size_t)km_lds_floats(D, KP, clusters, mode) * 4;
+    // mode 0 takes every shape w2e_cluster_assign takes ((D + 256) * {8,16,32} floats there): where six blocks of partial distances
+    // do not fit beside the centres, the three-block kernel runs.  KP = 24 has none: w2e_cluster_assign pads K = 17..24 to 32 and
+    // stops at D = 1024, the six-block form at D = 1315
+    const bool three = mode == KM_ASSIGN && KP != 24 && km_lds_floats(D, KP, clusters, mode) * 4 > 160 * 1024;
+    const size_t lds = (size_t)km_lds_floats(D, KP, clusters, mode, three ? 3 : 6) * 4;
     W2E_REQUIRE(lds <= 160 * 1024, "kmeans_pass: mode %d with %d clusters of %d dimensions needs %zu B of LDS", mode, clusters, D, lds);
     hipStream_t s = (hipStream_t)stream;
-    static unsigned done[9];
+    static unsigned done[12];
     int rc = 0;
-#define KM_GO(KP_, MODE_, slot)                                                                                                    \
-    rc = km_launch<KP_, MODE_>(&done[slot], lds, grid, s, feat, centroids, assign, mind, cand_dist, cand_ld, partial, channels, \
-                               pos_channels, size, clusters, (int)tiles, tiles_per_img)
+#define KM_GO3(KP_, MODE_, SLOTS_, slot)                                                                                          \
+    rc = km_launch<KP_, MODE_, SLOTS_>(&done[slot], lds, grid, s, feat, centroids, assign, mind, cand_dist, cand_ld, partial, \
+                                       channels, pos_channels, size, clusters, (int)tiles, tiles_per_img)
+#define KM_GO(KP_, MODE_, slot) KM_GO3(KP_, MODE_, 6, slot)
     if (mode == KM_SEED) KM_GO(8, KM_SEED, 8);
-    else if (mode == KM_ASSIGN) {
+    else if (three) {
+        if (KP == 8) KM_GO3(8, KM_ASSIGN, 3, 9);
+        else if (KP == 16) KM_GO3(16, KM_ASSIGN, 3, 10);
+        else KM_GO3(32, KM_ASSIGN, 3, 11);
+    } else if (mode == KM_ASSIGN) {
         if (KP == 8) KM_GO(8, KM_ASSIGN, 0);
         else if (KP == 16) KM_GO(16, KM_ASSIGN, 1);
         else if (KP == 24) KM_GO(24, KM_ASSIGN, 2);
@@ -273,6 +291,7 @@ extern "C" int w2e_kmeans_pass(int mode, const float* feat, const float* centroi
         else KM_GO(32, KM_STEP, 7);
     }
 #undef KM_GO
+#undef KM_GO3
     if (rc) return rc;
     W2E_LAUNCH_CHECK("kmeans_pass");
     return 0;
