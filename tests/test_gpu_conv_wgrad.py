@@ -1,5 +1,5 @@
 """Decoder fine-tuning on the MI355X: the conv-weight gradient of ModulatedConv2d (w2e_modconv_wgrad + w2e_modconv_wgrad_finish)
-against float64 -- kernel level (SAME / UP / centre tap, ragged channels, guard canaries), module level (the reference's own
+against float64 -- kernel level (SAME / UP / centre tap / DOWN / DOWN-CENTRE, ragged channels, guard canaries), module level (the reference's own
 gradients in tests/golden/modconv_wgrad.npz), generator level (the oracle's float64 autograd), bit reproducibility, graph
 capture with an optimizer step between replays, and the frozen path launching none of it."""
 import ctypes
@@ -26,19 +26,23 @@ def _heavy(shape, gen):
 
 
 def _reference_c(mode, g, x, d, s):
-    """C [Cout,Cin,taps] in float64 on the device (9 dgemms over the shifted operand)."""
+    """C [Cout,Cin,taps] in float64 on the device (9 dgemms over the shifted operand).  Modes 3 / 4 (DOWN / DOWN-CENTRE): g on the
+    output grid [h,w], x the [2h+1,2w+1] blurred input sampled at (2y + ky, 2x + kx); mode 4 the (1,1) tap only."""
     g, x = g.double(), x.double()
     if d is not None:
         g = g * d.double()[:, :, None, None]
     sx = x * s.double()[:, :, None, None]
     b, cin, h, w = x.shape
     cout = g.shape[1]
-    taps = [(1, 1)] if mode == 2 else [(ky, kx) for ky in range(3) for kx in range(3)]
+    taps = [(1, 1)] if mode in (2, 4) else [(ky, kx) for ky in range(3) for kx in range(3)]
     out = []
     for ky, kx in taps:
         if mode == 1:
             a = g[:, :, ky:ky + 2 * h:2, kx:kx + 2 * w:2]
             bb = sx
+        elif mode >= 3:
+            a = g
+            bb = sx[:, :, ky:ky + 2 * g.shape[2]:2, kx:kx + 2 * g.shape[3]:2]
         else:
             a = g
             bb = torch.nn.functional.pad(sx, (1, 1, 1, 1))[:, :, ky:ky + h, kx:kx + w]
@@ -54,8 +58,10 @@ def _raw_wgrad(mode, g, x, d, s, guard=64):
     from where2edit_amd._lib import call, ptr, stream_ptr
     _lib.load()
     b, cin, h, w = x.shape
+    if mode >= 3:  # DOWN / DOWN-CENTRE take the size of g; x is [2h+1, 2w+1]
+        h, w = g.shape[2], g.shape[3]
     cout = g.shape[1]
-    taps = 1 if mode == 2 else 9
+    taps = 1 if mode in (2, 4) else 9
     sp = ctypes.c_int(0)
     call("w2e_modconv_wgrad_plan", mode, b, cin, cout, h, w, ctypes.byref(sp))
     n = taps * cout * cin
@@ -87,6 +93,15 @@ KERNEL_CASES = [
     (2, 3, 16, 3, 6, 6),
     (2, 2, 36, 20, 33, 17),
     (2, 1, 3, 12, 256, 256),
+    # DOWN / DOWN-CENTRE: h, w are the size of g, x is [2h+1, 2w+1]
+    (3, 3, 20, 3, 4, 4),
+    (3, 2, 12, 20, 5, 33),
+    (3, 1, 3, 36, 9, 6),
+    (3, 4, 36, 12, 16, 16),
+    (4, 3, 3, 12, 7, 9),
+    (4, 2, 12, 20, 5, 33),
+    (4, 1, 36, 3, 9, 6),
+    (4, 4, 20, 36, 16, 16),
 ]
 
 
@@ -95,8 +110,9 @@ def test_wgrad_kernel_against_float64_correlation(case):
     mode, b, cin, cout, h, w = case
     gen = torch.Generator().manual_seed(hash(case) % (2 ** 31))
     gh, gw = (2 * h + 1, 2 * w + 1) if mode == 1 else (h, w)
+    xh, xw = (2 * h + 1, 2 * w + 1) if mode >= 3 else (h, w)
     g = _heavy((b, cout, gh, gw), gen).to(DEV)
-    x = _heavy((b, cin, h, w), gen).to(DEV)
+    x = _heavy((b, cin, xh, xw), gen).to(DEV)
     d = (torch.rand(b, cout, generator=gen) + 0.5).to(DEV)
     s = _heavy((b, cin), gen).to(DEV)
     dw, splits = _raw_wgrad(mode, g, x, d, s)
