@@ -183,17 +183,33 @@ def sd64(model):
 def _hip_activations(model, x):
     """{conv index: post-ReLU activation} of the HIP forward over the merged batch x (the `route` of lpips_ref.taps)."""
     from where2edit_amd import irse_hip as IR
-    from where2edit_amd import lpips as L
+    from where2edit_amd import vgg16 as V
     plan, acts = model.plan(), {}
     with torch.no_grad():
         h = IR.affine_act(x.contiguous(), plan.a, plan.b)
-        for r in L.SLICES:
-            for i in r:
-                if i in L.POOLS:
-                    h = L._maxpool(h)
-                elif i in L.CONVS:
-                    h = acts[i] = L._conv_relu(plan, i, h)
+        for k in range(5):
+            outs = V.slice_fwd(plan, k, h)
+            acts.update(zip(V.SLICE_CONVS[k], outs))
+            h = outs[-1]
     return {i: a.cpu() for i, a in acts.items()}
+
+
+def test_vgg16_and_lpips_run_one_trunk(model, w2e_opt):
+    """Vgg16 holding LPIPS's first ten convolutions gives, on the scaled input, the bits of LPIPS's own first four taps: the same
+    inputs in the same batch through the same calls (deterministic mode; odd height and width, so every pool floors)."""
+    from where2edit_amd import irse_hip as IR
+    from where2edit_amd.perceptual_loss import Vgg16, feature_state_dict
+    w2e_opt("deterministic", "1")
+    vgg = Vgg16()
+    vgg.load_state_dict(feature_state_dict(model.net.state_dict()), strict=True)  # its `slice{k}.{i}.*` keys; slice5 is ignored
+    vgg = vgg.to(DEV)
+    x = torch.cat(R.inputs((2, 3, 33, 47))).to(DEV)
+    plan = model.plan()
+    acts = _hip_activations(model, x)
+    with torch.no_grad():
+        outs = vgg(IR.affine_act(x, plan.a, plan.b))
+    for name, o, i in zip(outs._fields, outs, (2, 7, 14, 21)):
+        assert torch.equal(o.cpu(), acts[i]), name
 
 
 @pytest.mark.parametrize("wino", ["auto", False])

@@ -31,15 +31,13 @@ def _loss(size):
 
 def _hip_activations(vgg, x, slices=2):
     """{conv index: post-ReLU activation} of the HIP forward (the `route` of ref_vgg)."""
-    from where2edit_amd import perceptual_loss as PL
+    from where2edit_amd import vgg16 as V
     plan, acts, h = vgg.plan(), {}, x
     with torch.no_grad():
         for k in range(slices):
-            for i in PL.SLICES[k]:
-                if i in PL.POOLS:
-                    h = PL._maxpool(h)
-                elif i in PL.CONVS:
-                    h = acts[i] = PL._conv_relu(plan, i, h)
+            outs = V.slice_fwd(plan, k, h)
+            acts.update(zip(V.SLICE_CONVS[k], outs))
+            h = outs[-1]
     return {i: a.cpu() for i, a in acts.items()}
 
 
@@ -65,10 +63,10 @@ def _tie_input(shape, key):
 
 @pytest.mark.parametrize("shape", [(3, 5, 7, 9), (2, 67, 17, 20), (1, 3, 16, 16), (2, 3, 6, 10)])
 def test_maxpool_forward_equals_torch(shape):
-    from where2edit_amd.perceptual_loss import _maxpool
+    from where2edit_amd.vgg16 import maxpool
     x = _tie_input(shape, f"mp.fwd{shape}")
     x[0, 0, 2, 3] = float("nan")  # a NaN propagates (window (1, 1))
-    y = _maxpool(x.to(DEV)).cpu()
+    y = maxpool(x.to(DEV)).cpu()
     ref = F.max_pool2d(x, 2, 2)
     assert y.shape == ref.shape and torch.isnan(y[0, 0, 1, 1])
     torch.testing.assert_close(y, ref, rtol=0, atol=0, equal_nan=True)
@@ -76,15 +74,15 @@ def test_maxpool_forward_equals_torch(shape):
 
 @pytest.mark.parametrize("shape", [(3, 5, 7, 9), (2, 67, 17, 20), (1, 3, 16, 16), (2, 3, 6, 10)])
 def test_fused_pool_relu_backward_equals_float64_autograd(shape):
-    from where2edit_amd.perceptual_loss import _maxpool_bwd
-    x = _tie_input(shape, f"mp.bwd{shape}").double()
+    from where2edit_amd.vgg16 import maxpool_bwd
+    x =_tie_input(shape, f"mp.bwd{shape}").double()
     x[0, 0, 0:2, 2:4] = torch.tensor([[2.0, 2.0], [2.0, 1.0]], dtype=torch.float64)  # a positive exact tie: window (0, 1)
     b, c, h, w = shape
     g = seeded.tensor(f"mp.g{shape}", (b, c, h // 2, w // 2))
     xr = x.clone().requires_grad_(True)
     (ref,) = torch.autograd.grad((F.max_pool2d(F.relu(xr), 2, 2) * g.double()).sum(), xr)
     y = F.relu(x).float()  # the saved pool input (post-ReLU)
-    got = _maxpool_bwd(g.to(DEV), y.to(DEV), relu=True).cpu()
+    got = maxpool_bwd(g.to(DEV), y.to(DEV), relu=True).cpu()
     assert torch.equal(got.double(), ref)
     assert got[0, 0, 0, 2] == g[0, 0, 0, 1] and got[0, 0, 0, 3] == 0 and got[0, 0, 1, 2] == 0  # the first arg-max takes it
     if h % 2:
@@ -94,7 +92,7 @@ def test_fused_pool_relu_backward_equals_float64_autograd(shape):
     # relu=False: the pool's own adjoint (Vgg16's slice boundary), against autograd of max_pool2d alone
     yr = y.double().requires_grad_(True)
     (ref0,) = torch.autograd.grad((F.max_pool2d(yr, 2, 2) * g.double()).sum(), yr)
-    assert torch.equal(_maxpool_bwd(g.to(DEV), y.to(DEV), relu=False).cpu().double(), ref0)
+    assert torch.equal(maxpool_bwd(g.to(DEV), y.to(DEV), relu=False).cpu().double(), ref0)
 
 
 def _head(f1, f2, grad2=False):

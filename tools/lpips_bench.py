@@ -29,15 +29,15 @@ def stock_head(f0, f1, w):
 
 def stock_lpips(model, in0, in1):
     """The published composition on stock ops: both inputs through the scaling layer and the five slices, the literal head per tap."""
-    from where2edit_amd import lpips as L
+    from where2edit_amd import vgg16 as V
 
     def taps(x):
         h, outs = (x - model.scaling_layer.shift) / model.scaling_layer.scale, []
-        for k, r in enumerate(L.SLICES):
+        for k, r in enumerate(V.SLICES):
             for i in r:
-                if i in L.POOLS:
+                if i in V.POOLS:
                     h = F.max_pool2d(h, 2, 2)
-                elif i in L.CONVS:
+                elif i in V.CONVS:
                     conv = getattr(getattr(model.net, f"slice{k + 1}"), str(i))
                     h = F.relu(F.conv2d(h, conv.weight, conv.bias, padding=1))
             outs.append(h)

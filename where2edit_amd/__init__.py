@@ -13,6 +13,7 @@ Layout:
   clip_vit.py, clip_loss.py                criteria/clip_loss.py surface + ViT-B/32
   id_loss.py, irse_hip.py                  criteria/id_loss.py surface + IR-SE50 on the conv engine
   perceptual_loss.py                       criteria/perceptual_loss.py surface: VGG16 relu2_2 MSE on the conv engine
+  vgg16.py                the VGG16 trunk under perceptual_loss.py and lpips.py: table, module tree, checkpoint mapper, plan, slice walks
   derived.py              the one cache of tensors derived from frozen parameters, and invalidate (= stylegan2.invalidate_caches)
   coach.py, ranger.py     the mapper training step (mapper/training/coach.py:70-92) + optimizer
   _fused_opt.py           what Ranger and Adam share around their one-launch kernels (csrc/multi_tensor.h on the C side)

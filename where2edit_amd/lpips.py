@@ -5,8 +5,8 @@
   * the ScalingLayer `(x - shift) / scale` is w2e_affine_act_fwd (a per-channel affine map on three channels; it comes before the
     zero padding of conv1_1, so it cannot be folded into that convolution's bias);
   * the thirteen 3x3 convolutions of VGG16 configuration D are w2e_conv3x3 with bias and ReLU in the epilogue (the Winograd forms where
-    the library's plan picks them), the four 2x2 max-pools w2e_maxpool2x2_fwd / w2e_maxpool2x2_relu_bwd -- the kernels of
-    perceptual_loss.Vgg16, which stops at relu4_3; conv5 is three more calls and one more pool;
+    the library's plan picks them), the four 2x2 max-pools w2e_maxpool2x2_fwd / w2e_maxpool2x2_relu_bwd -- all of it vgg16.py,
+    the trunk perceptual_loss.Vgg16 runs to relu4_3; conv5 is its fifth slice;
   * the head is new: w2e_lpips_head_fwd / w2e_lpips_head_bwd (include/w2e_lpips.h, csrc/lpips.hip), one call per tap.
 
 Nothing of this was checked against the `lpips` package, torchvision or the published weight files: none of them is available where
@@ -34,32 +34,25 @@ and no stock-op fallback."""
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import functional as K
 from . import irse_hip as IR
+from . import vgg16 as V
 from ._lib import CONSTS, call, ptr, stream_ptr
 from .derived import derived
-from .perceptual_loss import _c, _maxpool, _maxpool_bwd
 
-# VGG16 configuration D (torchvision.models.vgg16().features): index -> (in, out) of each conv; ReLU after every conv, MaxPool2d(2, 2)
-# at 4, 9, 16 and 23.  The package cuts it into five slices, each ending at a tap.
-CONVS = {0: (3, 64), 2: (64, 64), 5: (64, 128), 7: (128, 128), 10: (128, 256), 12: (256, 256), 14: (256, 256), 17: (256, 512),
-         19: (512, 512), 21: (512, 512), 24: (512, 512), 26: (512, 512), 28: (512, 512)}
-POOLS = (4, 9, 16, 23)
-SLICES = (range(0, 4), range(4, 9), range(9, 16), range(16, 23), range(23, 30))
-TAPS = (2, 7, 14, 21, 28)  # relu1_2, relu2_2, relu3_3, relu4_3, relu5_3: the conv each tap follows
+TAPS = (2, 7, 14, 21, 28)  # relu1_2, relu2_2, relu3_3, relu4_3, relu5_3: the conv each tap follows, the last of each of V.SLICES
 CHANNELS = (64, 128, 256, 512, 512)
 SHIFT = (-.030, -.088, -.188)
 SCALE = (.458, .448, .450)
 HEAD_PARTIALS = CONSTS["W2E_LPIPS_PARTIALS"]  # floats of the head's partials slab per image (include/w2e_lpips.h)
-
-
-def _slice_of(i):
-    return next(k for k, r in enumerate(SLICES) if i in r) + 1
+# The names this module had while it held its own copy of the network: the trunk's table and kernel calls.  Code written against them
+# keeps working; nothing in the package uses them.
+CONVS, POOLS, SLICES = V.CONVS, V.POOLS, V.SLICES
+_conv_relu, _maxpool = V.conv_relu, V.maxpool
 
 
 def conv_names():
     """`net.slice{k}.{i}` of the thirteen convolutions, in network order."""
-    return [f"net.slice{_slice_of(i)}.{i}" for i in CONVS]
+    return [f"net.slice{V.slice_of(i)}.{i}" for i in V.CONVS]
 
 
 def state_dict_keys():
@@ -69,54 +62,23 @@ def state_dict_keys():
     return keys + [f"lin{k}.model.1.weight" for k in range(5)]
 
 
-def _find(sd, what, name, candidates, shape):
-    for key in candidates:
-        if key in sd:
-            break
-    else:
-        raise KeyError(f"{what}: no tensor for {name} (looked for {', '.join(candidates)})")
-    t = sd[key]
-    if tuple(t.shape) != shape:
-        raise RuntimeError(f"{what}: {key} has shape {tuple(t.shape)}, expected {shape}")
-    return t.detach().float()
-
-
-def _unwrap(sd):
-    return sd.get("state_dict", sd) if isinstance(sd, dict) else sd
-
-
 def lin_state_dict(sd):
     """The five lin weights of an LPIPS checkpoint, keyed `lin{k}.model.1.weight`, from the package's weights file
     (`lin{k}.model.1.weight`), its ModuleList alias (`lins.{k}.model.1.weight`) or a whole-module state_dict.  Other keys are ignored; a
     missing or misshapen tensor raises with the names it looked for."""
-    sd = _unwrap(sd)
+    sd = V.unwrap(sd)
     out = {}
     for k, c in enumerate(CHANNELS):
         name = f"lin{k}.model.1.weight"
-        out[name] = _find(sd, "LPIPS lin weights", name, (name, f"lins.{k}.model.1.weight"), (1, c, 1, 1))
+        out[name] = V.find(sd, "LPIPS lin weights", name, (name, f"lins.{k}.model.1.weight"), (1, c, 1, 1))
     return out
 
 
 def vgg_state_dict(sd):
     """The 26 feature tensors of a VGG16 checkpoint, keyed `net.slice{k}.{i}.{weight,bias}`, from torchvision's layout
-    (`features.{i}.*`), this module's (`net.slice{k}.{i}.*`) or the bare `slice{k}.{i}.*`: perceptual_loss.feature_state_dict's mapping,
-    extended to conv5.  Other keys are ignored; a missing or misshapen tensor raises with the names it looked for."""
-    sd = _unwrap(sd)
-    out = {}
-    for i, (cin, cout) in CONVS.items():
-        bare = f"slice{_slice_of(i)}.{i}"
-        for kind, shape in (("weight", (cout, cin, 3, 3)), ("bias", (cout,))):
-            name = f"net.{bare}.{kind}"
-            out[name] = _find(sd, "LPIPS VGG16 weights", name, (f"features.{i}.{kind}", name, f"{bare}.{kind}"), shape)
-    return out
-
-
-def _refuse_trainable(module):
-    if torch.is_grad_enabled() and any(p.requires_grad for p in module.parameters()):
-        raise RuntimeError(
-            "where2edit_amd: an LPIPS weight requires grad.  The HIP kernels treat LPIPS as a frozen critic -- as the perceptual loss "
-            "does (criteria/perceptual_loss.py builds Vgg16(requires_grad=False)) -- and produce input gradients only; there is no "
-            "stock-op fallback.  Call .requires_grad_(False) on it.")
+    (`features.{i}.*`), this module's (`net.slice{k}.{i}.*`) or the bare `slice{k}.{i}.*`.  Other keys are ignored; a missing or
+    misshapen tensor raises with the names it looked for."""
+    return V.state_dict(sd, 5, "net.", ("features.{i}", "net.{name}", "{name}"), "LPIPS VGG16 weights")
 
 
 class ScalingLayer(torch.nn.Module):
@@ -131,21 +93,12 @@ class _Vgg16Features(torch.nn.Module):
 
     def __init__(self, generator):
         super().__init__()
-        for k, r in enumerate(SLICES):
-            seq = torch.nn.Sequential()
-            for i in r:
-                if i in CONVS:
-                    cin, cout = CONVS[i]
-                    conv = torch.nn.Conv2d(cin, cout, kernel_size=3, padding=1)
-                    with torch.no_grad():  # torchvision's VGG init: kaiming_normal_(mode="fan_out", nonlinearity="relu"), zero bias
-                        conv.weight.copy_(torch.randn(conv.weight.shape, generator=generator) * (2.0 / (cout * 9)) ** 0.5)
-                        conv.bias.zero_()
-                    seq.add_module(str(i), conv)
-                elif i in POOLS:
-                    seq.add_module(str(i), torch.nn.MaxPool2d(kernel_size=2, stride=2))
-                else:
-                    seq.add_module(str(i), torch.nn.ReLU(inplace=True))
-            self.add_module(f"slice{k + 1}", seq)
+
+        def init(conv):  # torchvision's VGG init (kaiming_normal_(mode="fan_out", nonlinearity="relu"), zero bias), from `generator`
+            with torch.no_grad():
+                conv.weight.copy_(torch.randn(conv.weight.shape, generator=generator) * (2.0 / (conv.out_channels * 9)) ** 0.5)
+                conv.bias.zero_()
+        V.add_slices(self, 5, init)
 
 
 class NetLinLayer(torch.nn.Module):
@@ -160,45 +113,19 @@ class NetLinLayer(torch.nn.Module):
         self.model.add_module("1", conv)
 
 
-class _Plan:
-    """Packed, frozen parameters: forward pack, transposed-flipped pack (input gradient) and bias of the thirteen convolutions, the
-    ScalingLayer as y = a x + b, the five lin vectors."""
+class _Plan(V.Plan):
+    """The trunk's packed convolutions, the ScalingLayer as y = a x + b, the five lin vectors."""
 
     def __init__(self, model):
-        self.fwd, self.bwd, self.bias, self.cout = {}, {}, {}, {}
-        with torch.no_grad():
-            for i in CONVS:
-                conv = getattr(getattr(model.net, f"slice{_slice_of(i)}"), str(i))
-                w = conv.weight.detach().float()
-                self.fwd[i] = K.conv_pack(w, 1.0, transpose=False, flip=False)
-                self.bwd[i] = K.conv_pack(w, 1.0, transpose=True, flip=True)
-                self.bias[i] = conv.bias.detach().float().contiguous()
-                self.cout[i] = w.shape[0]
-            dev = self.bias[0].device
-            self.zero = {c: torch.zeros(c, device=dev, dtype=torch.float32) for c in (64, 128, 256, 512)}  # ReLU = PReLU(slope 0)
-            shift = model.scaling_layer.shift.detach().double().reshape(3)
-            scale = model.scaling_layer.scale.detach().double().reshape(3)
-            self.a = (1.0 / scale).float().contiguous()
-            self.b = (-shift / scale).float().contiguous()
-            self.lin = [getattr(model, f"lin{k}").model._modules["1"].weight.detach().float().reshape(-1).contiguous() for k in range(5)]
+        super().__init__(model.net, 5)
+        shift = model.scaling_layer.shift.detach().double().reshape(3)
+        scale = model.scaling_layer.scale.detach().double().reshape(3)
+        self.a = (1.0 / scale).float().contiguous()
+        self.b = (-shift / scale).float().contiguous()
+        self.lin = [getattr(model, f"lin{k}").model._modules["1"].weight.detach().float().reshape(-1).contiguous() for k in range(5)]
 
 
-# ---------------------------------------------------------------------------------------------- raw kernel calls
-def _conv_relu(plan, i, x):
-    _, _, h, w = x.shape
-    return IR.conv3x3(x, plan.fwd[i], plan.cout[i], h, w, bias=plan.bias[i], slope=plan.zero[plan.cout[i]])
-
-
-def _conv_grad(plan, i, g):
-    _, _, h, w = g.shape
-    return IR.conv3x3(g, plan.bwd[i], CONVS[i][0], h, w)
-
-
-def _relu_bwd(plan, g, y):
-    b, c, h, w = g.shape
-    return IR.affine_act_bwd(g, y, None, plan.zero[c], b, c, h, w)
-
-
+# ---------------------------------------------------------------------------------------------- the head's kernel calls
 def head_fwd(f0, f1, lin, out=None):
     """w2e_lpips_head_fwd: f0 [B,C,h,w], f1 [B or 1,C,h,w], lin [C] -> out [B]."""
     b, c = f0.shape[0], f0.shape[1]
@@ -234,20 +161,17 @@ class _LPIPS(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x0, x1, plan, need_grad, grad1):
-        x0, x1 = _c(x0), _c(x1)
+        x0, x1 = V.contig(x0), V.contig(x1)
         b0, b1 = x0.shape[0], x1.shape[0]
         rows = ((2 * b0 if grad1 else b0) if need_grad else 0)
         h = IR.affine_act(torch.cat([x0, x1]), plan.a, plan.b)
         taps, mids = [], []
         terms = torch.empty((5, b0), device=x0.device, dtype=torch.float32)
-        for k, r in enumerate(SLICES):
-            for i in r:
-                if i in POOLS:
-                    h = _maxpool(h)
-                elif i in CONVS:
-                    h = _conv_relu(plan, i, h)
-                    if i != TAPS[k] and need_grad:
-                        mids.append(h[:rows])
+        for k in range(5):
+            outs = V.slice_fwd(plan, k, h)
+            h = outs[-1]
+            if need_grad:
+                mids += [o[:rows] for o in outs[:-1]]
             taps.append(h)
             head_fwd(h[:b0], h[b0:], plan.lin[k], out=terms[k])
         total = ((terms[0] + terms[1]) + (terms[2] + terms[3])) + terms[4]
@@ -264,7 +188,7 @@ class _LPIPS(torch.autograd.Function):
         taps, mids = list(saved[:5]), list(saved[5:])
         plan, b0, grad1 = ctx.plan, ctx.b0, ctx.grad1
         rows = 2 * b0 if grad1 else b0
-        go = _c(go.reshape(-1).float())
+        go = V.contig(go.reshape(-1).float())
         g = None  # the gradient at the current tap (post-ReLU), arriving from the slice behind it
         for k in range(4, -1, -1):
             t = taps[k]
@@ -273,14 +197,11 @@ class _LPIPS(torch.autograd.Function):
                 g = torch.empty((rows,) + tuple(t.shape[1:]), device=t.device, dtype=torch.float32)
             # + the head's own gradient, then the tap's ReLU mask: the gradient at the pre-activation of the slice's last conv
             head_bwd(t[:b0], t[b0:], plan.lin[k], go, g0=g[:b0], g1=g[b0:] if grad1 else None, want_g1=grad1, accumulate=acc, relu=True)
-            convs = [i for i in SLICES[k] if i in CONVS]
-            inner = [mids.pop() for _ in range(len(convs) - 1)]  # the ReLU outputs in front of convs[-1], convs[-2], ...
-            for j in range(len(convs) - 1, -1, -1):
-                g = _conv_grad(plan, convs[j], g)
-                if j > 0:
-                    g = _relu_bwd(plan, g, inner[len(convs) - 1 - j])
+            n = len(V.SLICE_CONVS[k]) - 1  # the slice's ReLU outputs in between: the last n of what is left of mids
+            g = V.slice_bwd(plan, k, g, mids[len(mids) - n:])
+            del mids[len(mids) - n:]
             if k > 0:  # the pool's own adjoint: the previous tap's ReLU mask joins in its head call
-                g = _maxpool_bwd(g, taps[k - 1][:rows], relu=False)
+                g = V.maxpool_bwd(g, taps[k - 1][:rows], relu=False)
         b, _, h, w = g.shape
         g = IR.affine_act_bwd(g, None, plan.a, None, b, 3, h, w)  # gx = a[c] * gy (no activation behind the ScalingLayer)
         return g[:b0], (g[b0:] if grad1 else None), None, None, None
@@ -316,7 +237,7 @@ class LPIPS(torch.nn.Module):
         for k, c in enumerate(self.chns):
             self.add_module(f"lin{k}", NetLinLayer(c, g))
         if model_path is not None:
-            sd = _unwrap(torch.load(model_path, map_location="cpu"))
+            sd = V.unwrap(torch.load(model_path, map_location="cpu"))
             self.load_state_dict(lin_state_dict(sd), strict=False)
             if any(k.startswith("net.slice") for k in sd):
                 self.load_state_dict(vgg_state_dict(sd), strict=False)
@@ -331,19 +252,15 @@ class LPIPS(torch.nn.Module):
         return derived(self, "_plan", list(self.parameters()) + list(self.buffers()), lambda: _Plan(self))
 
     def forward(self, in0, in1, retPerLayer=False, normalize=False):
-        _refuse_trainable(self)
+        V.refuse_trainable(self, "LPIPS")
         for name, x in (("in0", in0), ("in1", in1)):
             if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != 3 or x.shape[2] < 16 or x.shape[3] < 16:
                 raise ValueError(f"LPIPS: {name} must be [B,3,H,W] with H, W >= 16, got "
                                  f"{tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
-        b0, b1 = in0.shape[0], in1.shape[0]
-        if tuple(in1.shape[1:]) != tuple(in0.shape[1:]) or (b1 != b0 and b1 != 1) or b0 < 1:
+        b0 = in0.shape[0]
+        if tuple(in1.shape[1:]) != tuple(in0.shape[1:]) or b0 < 1:
             raise ValueError(f"LPIPS: in1 {tuple(in1.shape)} must have in0's shape {tuple(in0.shape)}, or batch 1 of it")
-        grad_on = torch.is_grad_enabled()
-        grad1 = grad_on and in1.requires_grad
-        if grad1 and b1 != b0:
-            raise RuntimeError("LPIPS: a broadcast (batch-1) in1 that requires grad is not supported; detach it or repeat it to in0's batch")
-        need_grad = grad_on and (in0.requires_grad or grad1)
+        need_grad, grad1 = V.pair_grads("LPIPS", in0, in1, "in0", "in1")
         if normalize:
             in0, in1 = 2 * in0 - 1, 2 * in1 - 1
         in1 = in1 if grad1 else in1.detach()

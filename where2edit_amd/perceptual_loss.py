@@ -1,6 +1,6 @@
 """criteria/perceptual_loss.py surface: `PerceptualLoss(opts)(image1, image2) -> MSE(relu2_2(pre(image1)), relu2_2(pre(image2)))`
 with `pre = avg_pool(upsample(.))` and the `.model` (a `Vgg16`), `.upsample`, `.avg_pool` attributes of the reference, on the
-hand-written kernels of include/w2e_irse.h:
+hand-written kernels of include/w2e_irse.h (the network itself is vgg16.py, the trunk shared with lpips.py):
 
   * every 3x3 convolution is w2e_conv3x3 (mode SAME, bias and a zero-slope PReLU = ReLU in its epilogue; the Winograd forms
     where irse_hip._wino_form picks them, as for IR-SE50); input gradients through the transposed, flipped pack;
@@ -25,119 +25,24 @@ from collections import namedtuple
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import functional as K
 from . import irse_hip as IR
+from . import vgg16 as V
 from ._lib import call, ptr, stream_ptr
 from .derived import derived
 
 VggOutputs = namedtuple("VggOutputs", ["relu1_2", "relu2_2", "relu3_3", "relu4_3"])
 
-# VGG16 configuration D up to relu4_3 (torchvision.models.vgg16().features[:23]): index -> (in, out) of each conv; the others are
-# ReLU(inplace=True) after every conv and MaxPool2d(2, 2) at 4, 9 and 16.
-CONVS = {0: (3, 64), 2: (64, 64), 5: (64, 128), 7: (128, 128), 10: (128, 256), 12: (256, 256), 14: (256, 256), 17: (256, 512),
-         19: (512, 512), 21: (512, 512)}
-POOLS = (4, 9, 16)
-SLICES = (range(0, 4), range(4, 9), range(9, 16), range(16, 23))  # perceptual_loss.py:33-40
-
-
-def _slice_of(i):
-    return next(k for k, r in enumerate(SLICES) if i in r) + 1
-
-
-def _features():
-    layers = []
-    for i in range(23):
-        if i in CONVS:
-            conv = torch.nn.Conv2d(*CONVS[i], kernel_size=3, padding=1)
-            torch.nn.init.kaiming_normal_(conv.weight, mode="fan_out", nonlinearity="relu")  # torchvision's VGG init
-            torch.nn.init.constant_(conv.bias, 0)
-            layers.append(conv)
-        elif i in POOLS:
-            layers.append(torch.nn.MaxPool2d(kernel_size=2, stride=2))
-        else:
-            layers.append(torch.nn.ReLU(inplace=True))
-    return layers
+# The names this module had while it held the network itself: the trunk's table restricted to Vgg16's four slices, and the kernel calls.
+# Code written against them keeps working; nothing in the package uses them.
+CONVS, POOLS, SLICES = V.convs(4), V.POOLS[:3], V.SLICES[:4]
+_conv_relu, _maxpool, _maxpool_bwd = V.conv_relu, V.maxpool, V.maxpool_bwd
 
 
 def feature_state_dict(sd):
     """The 20 feature tensors of a VGG16 checkpoint, keyed `slice{k}.{i}.{weight,bias}`, from either torchvision's layout
     (`features.{i}.*`) or this module's (`slice{k}.{i}.*`, optionally under `model.`).  Other keys are ignored (`classifier.*`,
     torchvision's conv5 block); a missing or misshapen feature tensor raises."""
-    sd = sd.get("state_dict", sd) if isinstance(sd, dict) else sd
-    out = {}
-    for i, (cin, cout) in CONVS.items():
-        name = f"slice{_slice_of(i)}.{i}"
-        for kind, shape in (("weight", (cout, cin, 3, 3)), ("bias", (cout,))):
-            for key in (f"features.{i}.{kind}", f"{name}.{kind}", f"model.{name}.{kind}"):
-                if key in sd:
-                    break
-            else:
-                raise KeyError(f"VGG16 weights: no tensor for {name}.{kind} (looked for features.{i}.{kind}, {name}.{kind}, "
-                               f"model.{name}.{kind})")
-            t = sd[key]
-            if tuple(t.shape) != shape:
-                raise RuntimeError(f"VGG16 weights: {key} has shape {tuple(t.shape)}, expected {shape}")
-            out[f"{name}.{kind}"] = t.detach().float()
-    return out
-
-
-def _refuse_trainable(module):
-    if torch.is_grad_enabled() and any(p.requires_grad for p in module.parameters()):
-        raise RuntimeError(
-            "where2edit_amd: a VGG16 weight requires grad.  The HIP kernels treat VGG16 as a frozen critic -- as the perceptual loss "
-            "does (criteria/perceptual_loss.py builds Vgg16(requires_grad=False)) -- and produce input gradients only; there is no "
-            "stock-op fallback.  Construct Vgg16(requires_grad=False) or call .requires_grad_(False) on it.")
-
-
-class _Plan:
-    """Packed, frozen parameters of the ten convolutions: forward pack, transposed-flipped pack (input gradient), bias."""
-
-    def __init__(self, vgg):
-        self.fwd, self.bwd, self.bias, self.cout = {}, {}, {}, {}
-        with torch.no_grad():
-            for i in CONVS:
-                conv = getattr(getattr(vgg, f"slice{_slice_of(i)}"), str(i))
-                w = conv.weight.detach().float()
-                self.fwd[i] = K.conv_pack(w, 1.0, transpose=False, flip=False)
-                self.bwd[i] = K.conv_pack(w, 1.0, transpose=True, flip=True)
-                self.bias[i] = conv.bias.detach().float().contiguous()
-                self.cout[i] = w.shape[0]
-            dev = self.bias[0].device
-            self.zero = {c: torch.zeros(c, device=dev, dtype=torch.float32) for c in (64, 128, 256, 512)}  # ReLU = PReLU(slope 0)
-
-
-# ---------------------------------------------------------------------------------------------- raw kernel calls
-def _conv_relu(plan, i, x):
-    b, _, h, w = x.shape
-    return IR.conv3x3(x, plan.fwd[i], plan.cout[i], h, w, bias=plan.bias[i], slope=plan.zero[plan.cout[i]])
-
-
-def _conv_grad(plan, i, g, in_scale=None):
-    b, _, h, w = g.shape
-    return IR.conv3x3(g, plan.bwd[i], CONVS[i][0], h, w, in_scale=in_scale)
-
-
-def _relu_bwd(plan, g, y):
-    b, c, h, w = g.shape
-    return IR.affine_act_bwd(g, y, None, plan.zero[c], b, c, h, w)
-
-
-def _maxpool(x):
-    b, c, h, w = x.shape
-    y = torch.empty((b, c, h // 2, w // 2), device=x.device, dtype=torch.float32)
-    call("w2e_maxpool2x2_fwd", ptr(x), ptr(y), b * c, h, w, stream_ptr())
-    return y
-
-
-def _maxpool_bwd(g, x, relu):
-    b, c, h, w = x.shape
-    gx = torch.empty((b, c, h, w), device=g.device, dtype=torch.float32)
-    call("w2e_maxpool2x2_relu_bwd", ptr(g), ptr(x), ptr(gx), b * c, h, w, int(relu), stream_ptr())
-    return gx
-
-
-def _c(t):
-    return t if t.is_contiguous() else t.contiguous()
+    return V.state_dict(sd, 4, "", ("features.{i}", "{name}", "model.{name}"), "VGG16 weights")
 
 
 # ---------------------------------------------------------------------------------------------- autograd
@@ -146,33 +51,21 @@ class _Slice(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, plan, k):
-        x = _c(x)
-        r = SLICES[k]
-        pooled = r.start in POOLS
-        h = _maxpool(x) if pooled else x
-        outs = []
-        for i in r:
-            if i in CONVS:
-                h = _conv_relu(plan, i, h)
-                outs.append(h)
-        ctx.plan, ctx.k, ctx.pooled = plan, k, pooled
-        ctx.save_for_backward(*(([x] if pooled else []) + outs))
-        return h
+        x = V.contig(x)
+        outs = V.slice_fwd(plan, k, x)
+        ctx.plan, ctx.k, ctx.pooled = plan, k, V.SLICES[k].start in V.POOLS
+        ctx.save_for_backward(*(([x] if ctx.pooled else []) + outs))
+        return outs[-1]
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
         saved = ctx.saved_tensors
-        plan = ctx.plan
         x, outs = (saved[0], saved[1:]) if ctx.pooled else (None, saved)
-        convs = [i for i in SLICES[ctx.k] if i in CONVS]
-        g = _relu_bwd(plan, _c(gy), outs[-1])  # the slice's last ReLU
-        for j in range(len(convs) - 1, -1, -1):
-            g = _conv_grad(plan, convs[j], g)
-            if j > 0:
-                g = _relu_bwd(plan, g, outs[j - 1])
+        g = V.relu_bwd(ctx.plan, V.contig(gy), outs[-1])  # the slice's last ReLU
+        g = V.slice_bwd(ctx.plan, ctx.k, g, outs[:-1])
         if ctx.pooled:  # the gradient at the slice's input: the pool's own adjoint, no ReLU folded (the previous slice applies its own)
-            g = _maxpool_bwd(g, x, relu=False)
+            g = V.maxpool_bwd(g, x, relu=False)
         return g, None, None
 
 
@@ -184,7 +77,7 @@ class _PerceptualMSE(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x1, x2, plan, pre, need_grad, grad2):
-        x1, x2 = _c(x1), _c(x2)
+        x1, x2 = V.contig(x1), V.contig(x2)
         b1, b2 = x1.shape[0], x2.shape[0]
         if pre:
             size = x1.shape[-1]
@@ -194,10 +87,8 @@ class _PerceptualMSE(torch.autograd.Function):
             call("w2e_clip_preproc_fwd", ptr(x2), ptr(buf[b1:]), b2 * 3, size, st)
         else:
             buf = torch.cat([x1, x2])
-        r11 = _conv_relu(plan, 0, buf)
-        r12 = _conv_relu(plan, 2, r11)
-        r21 = _conv_relu(plan, 5, _maxpool(r12))
-        r22 = _conv_relu(plan, 7, r21)
+        r11, r12 = V.slice_fwd(plan, 0, buf)
+        r21, r22 = V.slice_fwd(plan, 1, r12)
         per = r22[0].numel()
         rows = (2 * b1 if grad2 else b1) if need_grad else 0
         gpre = torch.empty((rows,) + tuple(r22.shape[1:]), device=x1.device, dtype=torch.float32) if need_grad else None
@@ -218,13 +109,9 @@ class _PerceptualMSE(torch.autograd.Function):
         plan, b1 = ctx.plan, ctx.b1
         rows = gpre.shape[0]
         scale = go.reshape(1, 1).expand(rows, 128).contiguous()  # grad_output, on the device: conv2_2's input scale
-        g = _conv_grad(plan, 7, gpre, in_scale=scale)
-        g = _relu_bwd(plan, g, r21)
-        g = _conv_grad(plan, 5, g)
-        g = _maxpool_bwd(g, r12, relu=True)  # pool1 + relu1_2
-        g = _conv_grad(plan, 2, g)
-        g = _relu_bwd(plan, g, r11)
-        g = _conv_grad(plan, 0, g)
+        g = V.slice_bwd(plan, 1, gpre, [r21], in_scale=scale)
+        g = V.maxpool_bwd(g, r12, relu=True)  # pool1 + relu1_2
+        g = V.slice_bwd(plan, 0, g, [r11])
         if not ctx.pre:
             return g[:b1], (g[b1:] if ctx.grad2 else None), None, None, None, None
         st = stream_ptr()
@@ -245,24 +132,20 @@ class Vgg16(torch.nn.Module):
 
     def __init__(self, requires_grad=False):
         super().__init__()
-        features = _features()
-        self.slice1 = torch.nn.Sequential()
-        self.slice2 = torch.nn.Sequential()
-        self.slice3 = torch.nn.Sequential()
-        self.slice4 = torch.nn.Sequential()
-        for k, r in enumerate(SLICES):
-            for x in r:
-                getattr(self, f"slice{k + 1}").add_module(str(x), features[x])
+        def init(conv):  # torchvision's VGG init, from the global RNG
+            torch.nn.init.kaiming_normal_(conv.weight, mode="fan_out", nonlinearity="relu")
+            torch.nn.init.constant_(conv.bias, 0)
+        V.add_slices(self, 4, init)
         if not requires_grad:
             for param in self.parameters():
                 param.requires_grad = False
 
     def plan(self):
         """The packed parameters (cached: derived.py)."""
-        return derived(self, "_plan", list(self.parameters()), lambda: _Plan(self))
+        return derived(self, "_plan", list(self.parameters()), lambda: V.Plan(self, 4))
 
     def forward(self, X):
-        _refuse_trainable(self)
+        V.refuse_trainable(self, "VGG16")
         if X.dim() != 4 or X.shape[1] != 3 or X.shape[2] < 16 or X.shape[3] < 16:
             raise ValueError(f"Vgg16: expected [B,3,H,W] with H, W >= 16, got {tuple(X.shape)}")
         plan = self.plan()
@@ -314,16 +197,8 @@ class PerceptualLoss(torch.nn.Module):
         return self.avg_pool(self.upsample(image))
 
     def forward(self, image1, image2):
-        _refuse_trainable(self.model)
-        b1, b2 = image1.shape[0], image2.shape[0]
-        if b2 != b1 and b2 != 1:
-            raise ValueError(f"PerceptualLoss: target batch {b2} is neither the image batch {b1} nor 1")
-        grad_on = torch.is_grad_enabled()
-        grad2 = grad_on and image2.requires_grad
-        if grad2 and b2 != b1:
-            raise RuntimeError("PerceptualLoss: a broadcast (batch-1) target that requires grad is not supported; detach it or repeat it "
-                               "to the image batch")
-        need_grad = grad_on and (image1.requires_grad or grad2)
+        V.refuse_trainable(self.model, "VGG16")
+        need_grad, grad2 = V.pair_grads("PerceptualLoss", image1, image2, "image", "target")
         plan = self.model.plan()
         if self._closed_form(image1) and self._closed_form(image2):
             x1, x2, pre = image1, image2, True
