@@ -72,6 +72,8 @@ _IMAGE_IO = ("resample_tables", "resize_u8", "to_tensor", "label_ids", "to_bytes
              "save_image", "jpeg_parse", "jpeg_decode_states", "jpeg_decode_coefficients", "jpeg_pixels", "from_jpeg", "load_image",
              "png_parse", "png_plan", "png_inflate", "png_pixels", "from_png", "load_png", "read_image", "png_encode_plan", "png_filter", "png_deflate",
              "to_png", "save_png")
+_PROJECTOR = ("project", "save_projection", "noise_regularize", "noise_normalize_", "latent_noise", "latent_statistics", "loss_front",
+              "Projection")
 
 
 def __getattr__(name):
@@ -87,6 +89,9 @@ def __getattr__(name):
     if name in _EVALUATION:
         from . import evaluation
         return getattr(evaluation, name)
+    if name in _PROJECTOR:  # StyleGAN2's projector: w / W+ and the noise maps against LPIPS (projector.py, csrc/projector.hip)
+        from . import projector
+        return getattr(projector, name)
     if name in _IMAGE_IO:
         from . import image_io
         return getattr(image_io, name)

@@ -626,7 +626,9 @@ class _StyledConv(torch.autograd.Function):
     """Fused StyledConv: out = lrelu(d * conv(Wp, s*x) [blur] + nw*noise + bias) * sqrt2 with
     d = rsqrt(s^2 @ wsq^T + eps) (model.py:234-276, 285-290, op/fused_act.py); with fuse_act=False just
     d * conv(Wp, s*x) [blur] (a bare ModulatedConv2d).  Differentiable in x, s (direct + demodulation paths in one
-    gradient), noise_w, bias, and -- when the raw `weight` [1,Cout,Cin,k,k] is given (a layer opted in by
+    gradient), noise_w, bias, the shared noise map [1,1,oh,ow] (w2e_noise_grad: noise_w times the plane sum of the pre-activation
+    gradient, only when the map requires grad -- the projector's case; per-sample noise [B,1,H,W] with B > 1 never comes here, it keeps
+    stylegan2.StyledConv's unfused composition, where autograd gives the gradient) and -- when the raw `weight` [1,Cout,Cin,k,k] is given (a layer opted in by
     stylegan2.train_conv_weights) -- in the conv weight (w2e_modconv_wgrad + _finish; `wscale` = 1/sqrt(Cin*k^2)).  Without it
     the weight is frozen, as on the mapper path (coach.py:174-180 optimises net.mapper only), and no weight-gradient kernel runs."""
 
@@ -682,16 +684,19 @@ class _StyledConv(torch.autograd.Function):
         gx_full = _grad_rows((full, cin, h, w), n_skip, x.device) if n_skip else None
         gx_out = gx_full[n_skip:] if n_skip else None
         gs_full, gs_out = _zeros_with_tail(full, n_skip, (cin,), x.device, ctx.pool)
-        g_bias = g_nw = sums = dz = None
+        g_bias = g_nw = g_noise = sums = dz = None
         blurred = False
+        # the shared [1,1,oh,ow] noise map is being optimised (the projector): its gradient is one more read of the pre-activation gradient
+        want_noise = fuse_act and noise is not None and ctx.needs_input_grad[3]
         pre_sums = ctx.link.take(gout_full) if (fuse_act and ctx.link is not None) else None
         if pre_sums is not None:  # gout already IS the pre-activation gradient (the ToRGB backward applied the activation backward)
             gpre, sums = gout, pre_sums
         elif fuse_act:
             sums = torch.empty((b, cout, 3), device=x.device, dtype=torch.float32)
-            if upsample and _blur_actbwd_planned(b * cout, oh, ow, blur_kernel.shape):
+            if upsample and not want_noise and _blur_actbwd_planned(b * cout, oh, ow, blur_kernel.shape):
                 # wide up-sampling layers: activation backward, its three reductions and the adjoint blur in ONE pass over
-                # (gout, out) -- the pre-activation gradient is never written (3 tensor passes instead of 5)
+                # (gout, out) -- the pre-activation gradient is never written (3 tensor passes instead of 5); a noise map that needs a
+                # gradient needs that tensor, and takes the branch below with the separate adjoint blur
                 gpre = torch.empty((b, cout, oh + 1, ow + 1), device=x.device, dtype=torch.float32)
                 sp = profiling.span("upfirdn2d", 4.0 * b * cout * (2 * oh * ow + (oh + 1) * (ow + 1)))  # algorithmic bytes: gout + out + gT
                 call("w2e_blur_adjoint_actbwd", ptr(gout), ptr(out), ptr(noise), ptr(blur_kernel), ptr(gpre), ptr(sums), b * cout, oh, ow,
@@ -712,6 +717,9 @@ class _StyledConv(torch.autograd.Function):
                 g_bias = sums[..., 2].sum(0)
             if noise is not None and ctx.needs_input_grad[4]:
                 g_nw = sums[..., 1].sum().reshape(1)
+        if want_noise:  # before the adjoint blur: gpre is still [b, cout, oh, ow], the rows that carry a gradient
+            g_noise = torch.empty_like(noise)
+            call("w2e_noise_grad", ptr(gpre), ptr(noise_w), ptr(g_noise), b * cout, oh * ow, 0, stream_ptr())
         if upsample and not blurred:
             # adjoint of Blur(pad=(1,1)) back onto the (2h+1)x(2w+1) transposed-conv grid, then the
             # stride-2 conv that is the adjoint of conv_transpose2d
@@ -751,7 +759,7 @@ class _StyledConv(torch.autograd.Function):
                  ptr(bias) if fuse_act else None, ptr(d), ptr(s), ptr(wsq), ptr(gs), None, b, cin, cout, stream_ptr())
         if n_skip:
             gx = gx_full
-        return gx, gs_full, None, None, g_nw, g_bias, None, None, None, None, None, None, g_w, None, None
+        return gx, gs_full, None, g_noise, g_nw, g_bias, None, None, None, None, None, None, g_w, None, None
 
 
 def styled_conv(x, s, wsq, noise, noise_w, bias, packs, blur_kernel, upsample, link=None, demod=None, weight=None, wscale=1.0, fold=None):
